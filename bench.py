@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: batched DPLL on random 3-SAT n=100, alpha=4.26 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload P] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line.  --full adds everything else the benchmark measures or checks: the CPU
+baseline (oracle/, every host core), the oracle checks of the configs[3] and
+CDCL workloads, and at N = 1 every other BASELINE.json config in child
+processes (the line's `configs` object).  --dump-outputs DIR writes what the
+last timed step returned (dump_outputs below) as DIR/<name>.npy.
 
 A step = one pass of the hot path (csrc/dpll_scan.hip, SOUND mode, stop at the
 first model: the SAT/UNSAT decision) over one batch of synthetic uniform random
@@ -19,7 +26,7 @@ and the line's `verdict_sha` (the per-instance verdicts of the last step,
 gathered over RCCL) is the same for every N.
 
 --workload selects the other BASELINE.json configs (the default line is
-configs[2]; at N = 1 the default run also measures every other config in a
+configs[2]; at N = 1 a --full run also measures every other config in a
 child process after the headline -- the line's `configs` object):
     3sat-n50   configs[1]: 4,096 instances of n=50, alpha=4.26
     uf250      configs[4]: uf250-1065 shape (random 3-SAT n=250, m=1065),
@@ -90,7 +97,7 @@ RANDSETS = {"rand-res": ("res", 16, 7, 49, 7001), "rand-dp": ("dp", 16, 16, 96, 
 # CDCL preset: (formulas per step, clauses, max literals per clause, variables, max_iter, seed)
 CDCL = {"cdcl": (32768, 80, 3, 15, 10000, 1234)}
 
-# the secondary legs of the default N = 1 line: (name, workload, extra args)
+# the secondary legs of the --full N = 1 line: (name, workload, extra args)
 LEGS = [
     ("configs[1] 2 streams", "3sat-n50", ["--streams", "2", "--steps", "32", "--warmup", "4"]),
     ("configs[1] 16 streams", "3sat-n50", ["--streams", "16", "--steps", "128", "--warmup", "16"]),
@@ -138,7 +145,13 @@ def parse(argv=None):
     p.add_argument("--node-limit", type=int, default=None, help="dpll calls per instance (0 = none)")
     p.add_argument("--seed", type=int, default=20251016)
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also everything beside the headline figure: the CPU baseline and oracle checks, and at N = 1 "
+                        "every other BASELINE config (the line's `configs` object); off: only the timed steps")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="DPLL workloads: after the timed steps write what the last step returned as DIR/<name>.npy "
+                        "(float32 / float64, at most 64 MB: a fixed seeded sample of the instances if larger)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines and oracle checks")
     p.add_argument("--cpu-scaled", action="store_true",
                    help="searches too long for any bounded CPU sample (uf250 solved to the end): the CPU sample is "
                         "node-capped at --cpu-sample-node-limit and its unit-props/s scaled to instances/s by the "
@@ -150,8 +163,8 @@ def parse(argv=None):
     p.add_argument("--emulate-rank", type=int, default=0)
     p.add_argument("--full-json", default=None,
                    help="also write the uncompacted line (every leg's full objects) to this file")
-    p.add_argument("--no-legs", action="store_true", help="only the headline workload (no `configs` object)")
-    p.add_argument("--legs-only", action="store_true", help=argparse.SUPPRESS)   # the child of the default run
+    p.add_argument("--no-legs", action="store_true", help="--full with only the headline workload (no `configs` object)")
+    p.add_argument("--legs-only", action="store_true", help=argparse.SUPPRESS)   # the child of the --full run
     p.add_argument("--legs-hwq17", action="store_true", help=argparse.SUPPRESS)  # ... its HWQ17_LEGS child
     p.add_argument("--leg-cpu-seconds", type=float, default=4.0, help="CPU baseline budget of each leg")
     p.add_argument("--profile-steps", action="store_true", help="no warmup/cpu leg (for rocprofv3 runs)")
@@ -169,6 +182,10 @@ def parse(argv=None):
                    help="HIP streams (each with its own resident batch) the steps rotate over (default: 16 for "
                         "3sat-n50, whose 4,096 short searches leave most CU slots idle for a launch's 2 ms, else 2)")
     a = p.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.workload not in WORKLOADS:
+        p.error("--dump-outputs covers the DPLL workloads: " + ", ".join(sorted(WORKLOADS)))
     if a.workload in WORKLOADS:
         total, n, alpha, k, node_limit, a.config_name = WORKLOADS[a.workload]
         a.total = total if a.total is None else a.total
@@ -177,6 +194,18 @@ def parse(argv=None):
         a.k = k if a.k is None else a.k
         a.node_limit = node_limit if a.node_limit is None else a.node_limit
     return a
+
+
+def measures_cpu(args):
+    """The CPU baseline and the oracle checks: part of a --full run."""
+    return args.full and not args.no_cpu_baseline and not args.profile_steps
+
+
+def measures_legs(args, world):
+    """Every other BASELINE config after the headline: part of a --full run of
+    the default workload at its full size on one GPU."""
+    return (args.full and world == 1 and not args.no_legs and not args.profile_steps and args.workload == "3sat-n100"
+            and args.total == WORKLOADS["3sat-n100"][0] and not args.emulate_world)
 
 
 def init_ranks():
@@ -376,6 +405,43 @@ def batch_seed(seed, j):
     return seed + 7919 * j
 
 
+DUMP_BUDGET = 64 * 10**6      # --dump-outputs: bytes written in all
+DUMP_SAMPLE_SEED = 20251016   # ... the seed of the instance sample when all of them would not fit
+
+
+def dump_outputs(dirname, status, counters, sol_len, sol_lits, suffix="", budget=DUMP_BUDGET):
+    """--dump-outputs: what the last timed step's satmi_dpll_batch_device call
+    returned for this rank's B instances, as DIR/<name><suffix>.npy:
+
+        rows      float64 [R]      the instances kept (ascending indices into the batch)
+        status    float32 [R]      DPLL_* status
+        counters  float64 [R, 7]   nodes .. rounds (include/satmi.h SATMI_CTR_*), exact: < 2^53
+        sol_len   float32 [R]      literals of the first model (0: none)
+        sol_lits  float32 [R, n]   the model's literals, 0 past sol_len
+
+    The ticks counter is left out: it is the wave's time on the instance, not a
+    result.  R = B while everything fits in `budget` bytes, else the largest
+    count that fits, drawn without replacement by a generator seeded with
+    DUMP_SAMPLE_SEED: the same rows for the same B, n and budget."""
+    import numpy as np
+    B, n = sol_lits.shape
+    ncols = _capi.NCOUNTERS - 1
+    row_bytes = 8 + 4 + 8 * ncols + 4 + 4 * n
+    R = min(B, max(1, (budget - 5 * 4096) // row_bytes))   # (4 KiB per file for the .npy header)
+    rows = np.arange(B) if R == B else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, R, replace=False))
+    ix = torch.from_numpy(rows).to(sol_lits.device)
+    ln = sol_len[ix]
+    live = torch.arange(n, device=sol_lits.device)[None, :] < ln[:, None]
+    arrays = {"rows": rows.astype(np.float64),
+              "status": status[ix].to(torch.float32).cpu().numpy(),
+              "counters": counters[ix, :ncols].to(torch.float64).cpu().numpy(),
+              "sol_len": ln.to(torch.float32).cpu().numpy(),
+              "sol_lits": torch.where(live, sol_lits[ix], 0).to(torch.float32).cpu().numpy()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirname, name + suffix + ".npy"), arr)
+
+
 def run_dpll(args, world, rank, local):
     """One DPLL bench run (headline or leg): returns (line dict, host batch of the
     last step for the CPU baseline or None)."""
@@ -513,6 +579,8 @@ def run_dpll(args, world, rank, local):
         dist.all_reduce(seen)
     verdict_sha = hashlib.sha256(verdicts.cpu().numpy().tobytes()).hexdigest()[:16]
     icb, clb, lits, nv = batches[last]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, status, counters, sol_len, sol_lits, f".rank{rank}" if world > 1 else "")
 
     # roofline of the dominant kernel: algorithmic bytes per launch / average launch time
     read_bytes = B * (4 * m * k + 4 * m + 4 + 4) + 4
@@ -591,7 +659,7 @@ def run_dpll(args, world, rank, local):
         "branch_split": st if split_used else None,   # None: the last launch did not split (auto policy)
     }
     host = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_steps:
+    if rank == 0 and world == 1 and measures_cpu(args):
         host = cnf.CnfBatch(icb.cpu().numpy(), clb.cpu().numpy(), lits.cpu().numpy(), nv.cpu().numpy())
     return out, host
 
@@ -723,7 +791,7 @@ def run_saturation(args, world, rank, local):
            "roofline": saturation_roofline(stats, len({abs(l) for c in f for l in c})) if args.workload == "php-res" else
            dp_roofline(stats, done * world / elapsed, dp_launch_floor(stats))}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_steps:
+    if rank == 0 and world == 1 and measures_cpu(args):
         # the oracle on the same formula: checked against the GPU, then replicas
         # on every host core (oracle/cpu_pool.py)
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -817,7 +885,7 @@ def run_cdcl(args, world, rank, local):
            "roofline": issue_roofline(args.workload, nf, span_ms, kernel="cdcl")}
     r0 = res[0]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_steps:
+    if rank == 0 and world == 1 and measures_cpu(args):
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
         for i in range(0, nf, max(1, nf // 16)):   # verdicts checked against the oracle on a sample
@@ -891,7 +959,7 @@ def run_randset(args, world, rank, local):
     if kind == "res":
         out["derived_clauses_per_s"] = derived * world / elapsed
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.profile_steps:
+    if rank == 0 and world == 1 and measures_cpu(args):
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle
         # the oracle on the first formulas (resolution: ~2 s each on one core): verdicts
@@ -930,7 +998,7 @@ def run_one(args, world, rank, local):
 
 
 def legs_main(args):
-    """The default run's children: every other BASELINE config, short, one JSON
+    """The --full run's children: every other BASELINE config, short, one JSON
     object {name: compact line}.  Child processes so that the 16-stream leg
     gets a hardware queue per stream (GPU_MAX_HW_QUEUES, read at HIP start:
     --legs-hwq17 runs HWQ17_LEGS, the other child the rest)."""
@@ -938,12 +1006,13 @@ def legs_main(args):
     for name, wl, extra in LEGS:
         if (name in HWQ17_LEGS) != args.legs_hwq17:
             continue
-        a = parse(["--workload", wl, "--cpu-seconds", str(args.leg_cpu_seconds), "--seed", str(args.seed)] + extra)
+        a = parse(["--full", "--workload", wl, "--cpu-seconds", str(args.leg_cpu_seconds), "--seed", str(args.seed)]
+                  + extra)
         t = time.perf_counter()
         r = run_one(a, 1, 0, 0)
         r["leg_wall_s"] = time.perf_counter() - t
         out[name] = r
-        # progress on stderr (inherited by the parent: a long default run keeps
+        # progress on stderr (inherited by the parent: a long --full run keeps
         # telling a watchdog it is alive; stdout carries only the result)
         print(f"bench: leg {name!r} done in {r['leg_wall_s']:.1f} s", file=sys.stderr, flush=True)
     print(json.dumps(out), flush=True)
@@ -1027,9 +1096,7 @@ def main():
     out = run_one(args, world, rank, local)
     if rank == 0:
         print(f"bench: {args.workload} done in {time.perf_counter() - t_start:.1f} s", file=sys.stderr, flush=True)
-    legs = (world == 1 and not args.no_legs and not args.profile_steps and args.workload == "3sat-n100"
-            and args.total == WORKLOADS["3sat-n100"][0] and not args.emulate_world)
-    if legs and rank == 0:
+    if measures_legs(args, world) and rank == 0:
         got = {}
         for hwq in (False, True):
             env = dict(os.environ, GPU_MAX_HW_QUEUES="17") if hwq else dict(os.environ)
