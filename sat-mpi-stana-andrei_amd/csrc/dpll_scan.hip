@@ -658,11 +658,26 @@ __device__ uint32_t next_decision_epoch(const SLds<K, C> &S, int n, uint32_t ep)
     return 1;
 }
 
+// The decision literal `code` (its variable is free) as the one-entry batch of
+// epoch `ep`, assigned by the calling lane: what propagate()'s assignment loop
+// would do for the snapshot {code} -- trail slot tl, both state bytes, stamp
+// index 0 -- without the snapshot's write, read-back and stamp compare.
+// propagate(dec = true) advances tl over it.
+template <int K, typename C>
+__device__ __forceinline__ void assign_decision(const SLds<K, C> &S, int tl, uint32_t code, uint32_t ep) {
+    S.trail[tl] = (C)code;
+    lv_assign(S.lv, code);
+    S.ts[code >> 1] = stamp(ep, 0u);
+}
+
 // unit_propagate (REF.py:139-165) from the snapshot S.snap[0, nu), stamped
 // with epoch `ep` (the last epoch used; each scan takes the next).  Returns
 // true on conflict; `tl` ends where the reference stops (the assignments it
 // made, including the one that emptied a clause).  `dec`: the first batch is
 // the decision literal, which REF.py's counters do not count as a propagation.
+// The caller has assigned it already (assign_decision: trail[tl], its state
+// bytes, stamp index 0 of epoch `ep`), so the first round enters like a batch
+// a unit scan assigned itself (`pre`) and S.snap is not read for it.
 template <int K, bool INC, typename C>
 __device__ bool propagate(const SLds<K, C> &S, int mpad, int &tl, int nu, bool dec, uint32_t &ep, uint32_t &props,
                           uint32_t &rounds, PhaseClock &ph) {
@@ -673,7 +688,9 @@ __device__ bool propagate(const SLds<K, C> &S, int mpad, int &tl, int nu, bool d
     // kept) is not a propagation in REF.py's counters: taken off once here
     props -= dec ? 1u : 0u;
     ph.count(14);
-    int pre = -1;   // >= 0: the unit scan assigned the next batch itself (this many entries)
+    // >= 0: the batch is assigned already (this many entries) -- by the unit
+    // scan of the round before, or (first round) the decision by its caller
+    int pre = dec ? 1 : -1;
     while (nu > 0) {
         ++rounds;
         rs = tl;
@@ -1457,10 +1474,7 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
         }
         tl = tl0;
         wave_sync();
-        if (ln == 0) {
-            S.snap[0] = (C)dcode;
-            S.ts[dcode >> 1] = stamp(ep, 0u);
-        }
+        if (ln == 0) assign_decision<K>(S, tl, dcode, ep);
         c.decisions = 1;
         nu = 1;
         dec_round = true;
@@ -1506,8 +1520,7 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
                 if (ln == 0) {
                     S.fvar[depth] = (C)v;
                     S.ftrail[depth] = (C)tl;
-                    S.snap[0] = (C)(v << 1);                   // True first
-                    S.ts[v] = stamp(ep, 0u);
+                    assign_decision<K>(S, tl, v << 1, ep);     // True first
                 }
                 ++depth;
                 ++c.decisions;
@@ -1549,8 +1562,7 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
                 ep = next_decision_epoch<K>(S, n, ep);
                 if (ln == 0) {
                     S.fvar[top] = (C)(fv | SLds<K, C>::PHASE_BIT);
-                    S.snap[0] = (C)((fv << 1) | 1u);           // False
-                    S.ts[fv] = stamp(ep, 0u);
+                    assign_decision<K>(S, tl, (fv << 1) | 1u, ep);   // False
                 }
                 ++c.decisions;
                 ++c.nodes;
@@ -1605,8 +1617,7 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
                 ep = next_decision_epoch<K>(S, n, ep);
                 if (ln == 0) {
                     S.fvar[top] = (C)(fv | SLds<K, C>::PHASE_BIT);
-                    S.snap[0] = (C)((fv << 1) | 1u);               // False
-                    S.ts[fv] = stamp(ep, 0u);
+                    assign_decision<K>(S, tl, (fv << 1) | 1u, ep);   // False
                 }
                 ++c.decisions;
                 ++c.nodes;
