@@ -308,6 +308,21 @@ int satmi_dpll_split_busy(void *stream, int64_t *busy_ticks);
 int satmi_dpll_plan(int max_vars, int max_clauses, int max_lits, int max_clause_len, int mode, int has_init,
                     int *kernel, uint64_t *lds_bytes_per_wave, int *waves_per_cu);
 
+/* Which compiled form of the clause kernels a launch of this batch shape takes
+ * (inc != 0: incremental rounds, the AUTO / INC policies; 0: the SCAN policy).
+ * Launches nothing.  *K = literal slots of a clause word (3 or 5: 3-literal
+ * formulas with more than 511 variables are promoted to 5); *lv_class = bytes
+ * of the static literal-state array of the one-wave workgroup form (256, 512,
+ * 1024 for K = 3; 512, 4096 for K = 5), 0 = the literal states lie in each
+ * wave's dynamic LDS image (the 2- and 4-wave workgroup forms, and the fixed
+ * form); *waves_per_wg = 1, 2 or 4; *fixed = 1 for the static-layout kernel of
+ * the bench class (K = 3, <= 127 variables, <= 448 clauses, incremental).
+ * SATMI_ERR_ARG when the clause kernels do not take the shape.  The choice
+ * depends on the device's occupancy answer for each form, so it is a property
+ * of the shape and the device. */
+int satmi_dpll_scan_shape(int max_vars, int max_clauses, int max_clause_len, int inc, int *K, int *lv_class,
+                          int *waves_per_wg, int *fixed);
+
 #ifdef __cplusplus
 }
 #endif

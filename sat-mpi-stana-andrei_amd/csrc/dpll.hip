@@ -1280,6 +1280,19 @@ extern "C" int satmi_dpll_plan(int max_vars, int max_clauses, int max_lits, int 
     return SATMI_OK;
 }
 
+extern "C" int satmi_dpll_scan_shape(int max_vars, int max_clauses, int max_clause_len, int inc, int *K,
+                                     int *lv_class, int *waves_per_wg, int *fixed) {
+    if (!K || !lv_class || !waves_per_wg || !fixed) {
+        set_error("satmi_dpll_scan_shape: null output");
+        return SATMI_ERR_ARG;
+    }
+    const int rc = dpll_scan_shape(max_vars, max_clauses, max_clause_len, inc != 0, K, lv_class, waves_per_wg, fixed);
+    if (rc == SATMI_ERR_ARG)
+        set_error("satmi_dpll_scan_shape: shape not eligible for the clause kernels (clause lengths 1..5, <= 2047 "
+                  "variables)");
+    return rc;
+}
+
 extern "C" uint64_t satmi_dpll_lds_bytes(int max_vars, int max_clauses, int max_lits) {
     DpllLayout lay;
     if (!make_layout(max_vars, max_clauses, max_lits, &lay)) return 0;

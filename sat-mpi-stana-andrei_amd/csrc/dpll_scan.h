@@ -51,6 +51,13 @@ bool dpll_scan_eligible(int max_vars, int max_clauses, int max_lits, int max_cla
 int dpll_scan_resident(int max_vars, int max_clauses, int max_clause_len, bool inc, int *waves_per_cu,
                        uint32_t *lds_per_wave = nullptr);
 
+// The kernel form dpll_scan_launch would take for this shape: clause-word
+// slots K (3 / 5), the static literal-state class (256 / 512 / 1024 / 4096; 0 =
+// lv in each wave's dynamic image: the multi-wave workgroup form, and
+// dpll_fixed_kernel), waves per workgroup, and whether it is dpll_fixed_kernel.
+int dpll_scan_shape(int max_vars, int max_clauses, int max_clause_len, bool inc, int *K, int *lv_class,
+                    int *waves_per_wg, int *fixed);
+
 // Bytes of the splitting scratch head, and its statistics decoded from a host
 // copy of it: [donations, tickets, claims, reclaims, helpers, handoffs, done].
 constexpr int SPLIT_HEAD_BYTES = 512;

@@ -2108,6 +2108,20 @@ int dpll_scan_resident(int max_vars, int max_clauses, int max_clause_len, bool i
     return SATMI_OK;
 }
 
+int dpll_scan_shape(int max_vars, int max_clauses, int max_clause_len, bool inc, int *K, int *lv_class,
+                    int *waves_per_wg, int *fixed) {
+    const int k = pick_k(max_vars, max_clause_len);
+    if (!k) return SATMI_ERR_ARG;
+    ScanPlan P;
+    const int rc = scan_plan(k, max_vars, max_clauses, inc, &P);
+    if (rc) return rc;
+    *K = k;
+    *lv_class = P.lvs;
+    *waves_per_wg = P.waves_per_wg;
+    *fixed = P.fixed ? 1 : 0;
+    return SATMI_OK;
+}
+
 int dpll_scan_launch(const ScanLaunch &L) {
     const int K = pick_k(L.max_vars, L.max_clause_len);
     ScanPlan P;

@@ -33,7 +33,7 @@ EXPORTED = (
     "satmi_dp_last_stats",
     "satmi_cdcl_batch_host", "satmi_dpll_set_split_warmup", "satmi_resolution_debug_cand_bytes",
     "satmi_dp_trim", "satmi_resolution_trim", "satmi_cdcl_last_stats", "satmi_launch_chain_floor",
-    "satmi_dpll_split_busy",
+    "satmi_dpll_split_busy", "satmi_dpll_scan_shape",
 )
 
 
@@ -123,6 +123,7 @@ def load():
     L.satmi_dpll_launch_span.argtypes = [vp, vp]
     L.satmi_wallclock_hz.argtypes = [P(ctypes.c_double)]
     L.satmi_dpll_plan.argtypes = [ctypes.c_int] * 6 + [P(ctypes.c_int), P(ctypes.c_uint64), P(ctypes.c_int)]
+    L.satmi_dpll_scan_shape.argtypes = [ctypes.c_int] * 4 + [P(ctypes.c_int)] * 4
     L.satmi_dpll_batch_device.argtypes = [
         ctypes.c_int, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp,
         ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_int,
@@ -168,6 +169,16 @@ def plan(max_vars, max_clauses, max_lits, max_clause_len, mode=MODE_SOUND, has_i
                                  int(bool(has_init)), ctypes.byref(k), ctypes.byref(lds), ctypes.byref(w)),
           "satmi_dpll_plan")
     return k.value, lds.value, w.value
+
+
+def scan_shape(max_vars, max_clauses, max_clause_len, inc=True):
+    """(K, lv_class, waves_per_wg, fixed) of the clause-kernel form a launch of this batch shape takes
+    (satmi_dpll_scan_shape; inc=False: the KERNEL_SCAN policy).  Launches nothing."""
+    k, lvs, wpg, fixed = (ctypes.c_int(0) for _ in range(4))
+    check(load().satmi_dpll_scan_shape(int(max_vars), int(max_clauses), int(max_clause_len), int(bool(inc)),
+                                       ctypes.byref(k), ctypes.byref(lvs), ctypes.byref(wpg), ctypes.byref(fixed)),
+          "satmi_dpll_scan_shape")
+    return k.value, lvs.value, wpg.value, bool(fixed.value)
 
 
 def check(rc, what):

@@ -15,6 +15,11 @@ first model:
                90 s on the GPU, nor at alpha 17-19 in 30 s (tools/fullsolve_probe.py,
                profiles/r06/fullsolve_5sat_probe.txt); at alpha 12 all 64 finish
                (77 .. 2.6e5 nodes), which the oracle can follow
+    5sat50thr  random 5-SAT n=50, m=1056: the 5-SAT threshold itself (alpha
+               21.12) at the largest n the oracle follows cheaply -- 16
+               searches of 2.1e4 .. 2.2e5 nodes, 5 of them UNSAT: 5-literal
+               clause words exhausting both branches of every decision
+               (n=60 already needs 1.7e6 nodes; ~1 min on a few cores)
     python tests/golden/make_fullsolve.py [set]      (default: uf250)
 
 The checker is the C oracle (oracle/sat_oracle.c, SOUND mode), itself pinned to
@@ -44,7 +49,8 @@ SETS = {"uf250": (250, 1065, 3, 250, 96, 1_200_000),
         "unsat150": (150, 639, 3, 150, 24, 2_000_000),
         "unsat200": (200, 852, 3, 200, 12, 2_000_000),
         "uuf250": (250, 1065, 3, 2501, 16, 50_000_000),
-        "5sat200": (200, 2400, 5, 5200, 64, 2_000_000)}
+        "5sat200": (200, 2400, 5, 5200, 64, 2_000_000),
+        "5sat50thr": (50, 1056, 5, 5050, 16, 2_000_000)}
 SET = sys.argv[1] if len(sys.argv) > 1 else "uf250"
 N, M, K, SEED, COUNT, NODE_CAP = SETS[SET]
 OUT = os.path.join(HERE, f"fullsolve_{SET}.json")

@@ -93,6 +93,32 @@ def test_scan_kernel_eligibility_query():
         _capi.set_kernel(7)
 
 
+def test_scan_shape_query():
+    """satmi_dpll_scan_shape: the parts of the answer that no device changes --
+    the clause-word slots, the fixed class, the legal literal-state classes of
+    each K, and the shapes the clause kernels refuse.  (Which class and
+    workgroup width a shape gets on the MI355X is pinned by
+    test_dpll_gpu.py::test_scan_kernel_classes_decide_unsat.)"""
+    if not os.path.exists(_capi.LIB_PATH):
+        pytest.skip("libsatmi.so not built")
+    assert _capi.scan_shape(100, 426, 3) == (3, 0, 1, True)        # the bench class: dpll_fixed_kernel
+    assert _capi.scan_shape(127, 448, 3)[3] and not _capi.scan_shape(128, 448, 3)[3]
+    assert not _capi.scan_shape(127, 449, 3)[3]
+    assert not _capi.scan_shape(100, 426, 3, inc=False)[3]         # only the incremental policy has it
+    for n, m, klen, K in ((100, 426, 3, 3), (100, 426, 1, 3), (511, 100, 3, 3), (512, 100, 3, 5),
+                          (300, 100, 2, 3), (100, 426, 4, 5), (40, 300, 5, 5), (255, 200, 5, 5)):
+        for inc in (True, False):
+            k, lvs, wpg, fixed = _capi.scan_shape(n, m, klen, inc)
+            assert k == K, (n, m, klen, inc)
+            if not fixed:
+                assert lvs in ((0, 256, 512, 1024) if k == 3 else (0, 512, 4096)), (n, m, klen, inc, lvs)
+                assert wpg in (1, 2, 4) and (wpg == 1) == (lvs != 0), (n, m, klen, inc, lvs, wpg)
+                assert lvs == 0 or lvs >= 2 * (n + 1)              # the static array holds every literal state
+    for n, m, klen in ((2048, 100, 3), (100, 426, 6), (100, 426, 0)):
+        with pytest.raises(_capi.SatmiError):
+            _capi.scan_shape(n, m, klen)
+
+
 def test_split_policy_arguments():
     """satmi_dpll_set_split: 0 off / 1 auto / 2 always, helpers in [0, 32];
     satmi_dpll_set_split_warmup: < 0 restores the default (host-side state only)."""

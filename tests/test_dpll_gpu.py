@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
+import scan_cores
 from satmi import _capi, cnf
 from satmi.dpll import dpll_batch
 
@@ -165,7 +166,7 @@ def test_configs4_batch_properties(n, m, k, cap, B):
 
 
 @pytest.mark.parametrize("fixture,min_unsat", [("uf250", 0), ("unsat150", 5), ("unsat200", 5), ("uuf250", 5),
-                                               ("5sat200", 0)])
+                                               ("5sat200", 0), ("5sat50thr", 5)])
 @pytest.mark.parametrize("split", [_capi.SPLIT_OFF, _capi.SPLIT_ALWAYS])
 def test_configs4_solved_to_completion(golden_dir, fixture, min_unsat, split):
     """configs[4]-scale searches run to the end (no node cap): uf250-shaped SAT
@@ -173,12 +174,18 @@ def test_configs4_solved_to_completion(golden_dir, fixture, min_unsat, split):
     uuf250 shape itself (n=250, m=1065: 6 UNSAT searches of 2.5-8.5 M calls
     that exhaust both branches of every decision, REF.py:167-214, beside 10
     SAT ones), and 64 random 5-SAT n=200 searches (m=2400: five 12-bit codes
-    per clause word, the 5-literal LDS layout; 77 - 2.6e5 calls each) -- all
+    per clause word, the 5-literal LDS layout; 77 - 2.6e5 calls each), and 16
+    random 5-SAT n=50 searches at the 5-SAT threshold itself (m=1056: 5 UNSAT
+    ones that exhaust trees of 2.0e5 - 2.2e5 calls over 5-literal words) -- all
     decided: status, every counter and the model equal the oracle's
     (tests/golden/fullsolve_<fixture>.json, make_fullsolve.py), with and
     without branch splitting (a few searches on thousands of idle waves:
     helpers take subtrees of searches millions of calls deep).  Unsplit, a
-    search runs on one wavefront, so only the searches of <= 2 M calls run."""
+    search runs on one wavefront, so only the searches of <= 2 M calls run
+    (all 16 of 5sat50thr: 1.6 - 3.2 s unsplit on the MI355X, 0.2 s split).
+    The split statistics follow the launch: all zero after an unsplit one;
+    the split uuf250 run must show hand-offs (measured: 6,961 donations,
+    4,114 searches handed to their helpers) and busy wave ticks."""
     with open(os.path.join(golden_dir, f"fullsolve_{fixture}.json")) as fh:
         g = json.load(fh)
     batch = cnf.uniform_ksat(g["count"], g["n"], g["m"], g["k"], seed=g["seed"])
@@ -194,8 +201,25 @@ def test_configs4_solved_to_completion(golden_dir, fixture, min_unsat, split):
     _capi.set_split(split)
     try:
         r = dpll_batch(fs, mode="sound", max_solutions=1, sol_cap=1)   # a time limit would disable splitting
+        stats, busy = _capi.split_stats(None), _capi.split_busy(None)
     finally:
         _capi.set_split(_capi.SPLIT_AUTO)
+    if split == _capi.SPLIT_OFF:   # the stream's last launch did not split
+        assert busy == 0 and all(v == 0 for v in stats.values()), (busy, stats)
+    print(f"{fixture} split={split}: {stats}, busy ticks {busy}")
+    if fixture == "uuf250" and split == _capi.SPLIT_ALWAYS:
+        # searches of 2.5-8.5 M calls on thousands of helpers: donors reach branches their
+        # helpers still search and hand them the rest of their own search
+        assert stats["handoffs"] > 0 and stats["donations"] > 0, stats
+        assert busy > 0
+        # the statistics are the LAST launch's: an unsplit launch of the same kernel clears them
+        _capi.set_split(_capi.SPLIT_OFF)
+        try:
+            dpll_batch(fs[:2], mode="sound", max_solutions=1, sol_cap=1, node_limit=100)
+        finally:
+            _capi.set_split(_capi.SPLIT_AUTO)
+        assert _capi.split_busy(None) == 0
+        assert all(v == 0 for v in _capi.split_stats(None).values())
     for b, c in enumerate(cases):
         assert int(r.status[b]) == c["status"], c["index"]
         got = r.counter_dict(b)
@@ -547,6 +571,122 @@ def test_split_stats_reset_by_a_launch_that_does_not_split():
     finally:
         _capi.set_kernel(_capi.KERNEL_AUTO)
     assert all(v == 0 for v in _capi.split_stats(None).values())
+
+
+@pytest.mark.parametrize("n,m,policy", [(100, 426, _capi.KERNEL_AUTO), (140, 596, _capi.KERNEL_INC),
+                                        (140, 596, _capi.KERNEL_SCAN)])
+def test_split_stats_reset_by_an_unsplit_launch_of_the_clause_kernels(n, m, policy):
+    """The same "last launch" contract for the clause kernels themselves
+    (dpll_fixed_kernel at n=100, dpll_scan_kernel incremental and plain at
+    n=140): after a split launch, a SPLIT_OFF launch of the same kernel on the
+    same stream leaves satmi_dpll_split_stats all zero and
+    satmi_dpll_split_busy 0; a split launch after it reports again."""
+    batch = cnf.uniform_ksat(32, n, m, 3, seed=99)
+    _run_split(batch, True, policy, max_solutions=1, sol_cap=1)
+    st = _capi.split_stats(None)
+    assert st["done"] > 0 and st["donations"] > 0, st
+    assert _capi.split_busy(None) > 0
+    ru = _run_split(batch, False, policy, max_solutions=1, sol_cap=1)
+    assert _capi.split_busy(None) == 0
+    assert all(v == 0 for v in _capi.split_stats(None).values())
+    rs = _run_split(batch, True, policy, max_solutions=1, sol_cap=1)
+    assert _capi.split_stats(None)["done"] > 0 and _capi.split_busy(None) > 0
+    assert (rs.counters[:, :7] == ru.counters[:, :7]).all() and (rs.sol_lits == ru.sol_lits).all()
+
+
+# test_scan_kernel_classes_decide_unsat: (core, N) -> the (K, lv_class,
+# waves_per_wg) form of dpll_scan_kernel that _capi.scan_shape() reports on the
+# MI355X for the core renamed into 1..N, under the incremental and the plain
+# scan policy.  Read off the device once and frozen: scan_plan() weighs the LDS
+# image against each form's register occupancy, so the form jumps between
+# neighbouring N and between the two policies.  Together the rows reach, under
+# each policy, K=3 at 256 / 512 / 1024 / 0 and K=5 at 512 / 4096 / 0, the
+# workgroup forms (class 0) at both 2 and 4 waves, and every code-width edge
+# (127 / 128, 255 / 256, 511 / 512, 2047) with a variable on N itself.
+SCAN_CLASS_ROWS = [
+    # core, N, incremental, plain scan
+    ("A", 40, (5, 512, 1), (5, 0, 2)),
+    ("A", 255, (5, 512, 1), (5, 512, 1)),
+    ("A", 256, (5, 0, 2), (5, 0, 4)),
+    ("A", 300, (5, 0, 2), (5, 0, 2)),
+    ("A", 400, (5, 0, 4), (5, 4096, 1)),
+    ("A", 600, (5, 4096, 1), (5, 4096, 1)),
+    ("A", 2047, (5, 4096, 1), (5, 4096, 1)),
+    ("B", 255, (5, 512, 1), (5, 512, 1)),
+    ("B", 300, (5, 0, 4), (5, 0, 2)),
+    ("B", 2047, (5, 4096, 1), (5, 4096, 1)),
+    ("C", 127, (3, 256, 1), (3, 256, 1)),
+    ("C", 128, (3, 0, 2), (3, 512, 1)),
+    ("C", 255, (3, 512, 1), (3, 512, 1)),
+    ("C", 256, (3, 0, 4), (3, 0, 4)),
+    ("C", 280, (3, 1024, 1), (3, 0, 2)),   # the plain scan's 2-wave K=3 form
+    ("C", 300, (3, 0, 2), (3, 1024, 1)),
+    ("C", 400, (3, 1024, 1), (3, 1024, 1)),
+    ("C", 511, (3, 1024, 1), (3, 1024, 1)),
+    ("C", 512, (5, 0, 4), (5, 4096, 1)),   # 3-literal clauses promoted to the 5-slot word, two pads
+    ("C", 1500, (5, 4096, 1), (5, 0, 4)),
+]
+
+
+def test_scan_class_rows_cover_every_form():
+    for col in (2, 3):
+        forms = {r[col] for r in SCAN_CLASS_ROWS}
+        assert {(k, lvs) for k, lvs, _ in forms} == {(3, 256), (3, 512), (3, 1024), (3, 0), (5, 512), (5, 4096), (5, 0)}
+        assert {(k, w) for k, lvs, w in forms if lvs == 0} == {(3, 2), (3, 4), (5, 2), (5, 4)}
+        assert all((w == 1) == (lvs != 0) for _, lvs, w in forms)
+    for n in (127, 128, 255, 256, 511, 512, 2047):
+        assert any(r[1] == n for r in SCAN_CLASS_ROWS)
+
+
+def _scan_class_mismatches(core, N, want_inc, want_scan):
+    """Run one row of SCAN_CLASS_ROWS; returns the list of everything that differs from the oracle."""
+    img = scan_cores.renaming(core, N)
+    fs = [scan_cores.rename(f, img) for f in scan_cores.core_formulas(core)]
+    base = scan_cores.core_oracle(core)   # once per core per process
+    assert sum(o["status"] == _capi.DPLL_EXHAUSTED for o in base) >= 2
+    max_vars, max_clauses, _ = cnf.pack(fs).maxima()
+    assert max_vars == N   # the top code of the class is occupied
+    klen = max(len(c) for f in fs for c in f)
+    bad = []
+    for kern, want in ((_capi.KERNEL_INC, want_inc), (_capi.KERNEL_SCAN, want_scan)):
+        shape = _capi.scan_shape(max_vars, max_clauses, klen, inc=kern == _capi.KERNEL_INC)
+        if shape != want + (False,):
+            bad.append(f"kernel {kern}: form {shape}, expected {want}")
+        for split in (False, True):
+            r = _run_split(fs, split, kern, warmup=0, max_solutions=1, sol_cap=1)   # no node or time limit
+            tag = f"kernel {kern} split {split}"
+            st = _capi.split_stats(None)
+            if split and not st["donations"] > 0:
+                bad.append(f"{tag}: no donation {st}")
+            if not split and any(st.values()):
+                bad.append(f"{tag}: statistics of an unsplit launch {st}")
+            for b, o in enumerate(base):
+                if int(r.status[b]) != o["status"]:
+                    bad.append(f"{tag} instance {b}: status {int(r.status[b])} oracle {o['status']}")
+                got = r.counter_dict(b)
+                for key in CTR:
+                    if got[key] != o["counters"][key]:
+                        bad.append(f"{tag} instance {b}: {key} {got[key]} oracle {o['counters'][key]}")
+                if r.solutions(b)[:1] != scan_cores.rename(o["solutions"][:1], img):
+                    bad.append(f"{tag} instance {b}: model differs")
+    return bad
+
+
+@pytest.mark.parametrize("core,N,want_inc,want_scan", SCAN_CLASS_ROWS,
+                         ids=[f"{r[0]}-{r[1]}" for r in SCAN_CLASS_ROWS])
+def test_scan_kernel_classes_decide_unsat(core, N, want_inc, want_scan):
+    """Every compiled layout class of dpll_scan_kernel decides searches that
+    exhaust a tree: a small hard core (tests/scan_cores.py: 5-SAT, 4-SAT and
+    3-SAT formulas of 1.4e3 - 2.8e4 calls, at least two UNSAT per batch)
+    renamed into 1..N with a variable on N itself, so that the identical search
+    runs under the literal-state class, code width and workgroup form of N
+    variables.  The form the launch takes is asserted (_capi.scan_shape), then
+    the incremental and the plain scan kernel, unsplit and split from the first
+    check (warm-up 0), must give the oracle's status, six counters and model
+    of the un-renamed core, mapped through the renaming
+    (tests/test_oracle_renaming.py pins that equivariance on the CPU)."""
+    bad = _scan_class_mismatches(core, N, want_inc, want_scan)
+    assert not bad, f"{len(bad)} mismatches, first: {bad[:12]}"
 
 
 @pytest.mark.parametrize("seed,nmax,kmax,mmax", [(11, 12, 4, 60), (12, 400, 300, 30)])
