@@ -14,6 +14,12 @@
  *   activity     float64 arithmetic exactly as Python's (REF.py:355-357, :378).
  * The solve loop stops after `max_iter` iterations (REF.py:247 has none; the
  * reference's caller times it out after 60 s, REF.py:417-437).
+ *
+ * oracle_cdcl_paths runs the same search and also counts, in the GPU kernel's
+ * terms, which of its code paths the formula drives (CDCL_P_* below, named in
+ * oracle.py CDCL_PATHS): tests/cdcl_paths.py holds the formulas that reach
+ * each one, tests/test_cdcl_paths.py proves they do.  The counters only read
+ * the search's state; `pc == NULL` (oracle_cdcl) skips them.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -25,6 +31,48 @@ typedef struct {
     int32_t *lits;
     int32_t len;
 } cl_t;
+
+/* Path counters, in the order of oracle.py CDCL_PATHS.  "max" counters of a
+ * position start at -1 (never seen), the others at 0.  Kernel constants they
+ * are stated against: 64 lanes, windows of 256 stream slots (CDCL_WCH = 4),
+ * CDCL_LITS_AHEAD = 3, WS_BITMAP_SLOTS = 4,096. */
+enum {
+    /* propagate, per pass, the key list frozen at entry */
+    CDCL_P_FALSE_KEY_INDEX_MAX,   /* highest dict index of a false key visited (>= 64: a second key batch) */
+    CDCL_P_STREAM_LEN_MAX,        /* largest sum of mask + 1 over one 64-key batch's false keys */
+    CDCL_P_CONFLICT_POS_MAX,      /* largest stream position, within its key batch, of a conflict */
+    CDCL_P_CONFLICT_LATER_CHUNK,  /* conflicts at stream positions 64 .. 255 (chunks 1-3 of the first window) */
+    CDCL_P_CONFLICT_LATER_WINDOW, /* conflicts at stream positions >= 256 */
+    CDCL_P_STRADDLE_MEMBERS,      /* members visited whose table began in an earlier 256-slot window */
+    CDCL_P_REPL_POS_MAX,          /* largest clause position of a replacement watch (>= 3: the tail loop) */
+    CDCL_P_TAIL_SKIP_SELF,        /* tail-loop positions (>= 3) skipped because they repeat the visited literal */
+    CDCL_P_DUP_VISIT_PASSES,      /* passes in which one clause was visited through two false keys */
+    /* analysis and learning */
+    CDCL_P_CONFLICT_LEN_MAX,
+    CDCL_P_LEARNED_LEN_MAX,
+    CDCL_P_MAXLEVEL_POS_MAX,      /* largest position of the first literal at the maximal level */
+    CDCL_P_LEARNED_REPEAT_LE64,   /* learned clauses repeating a variable, <= 64 entries (the lanes' bump) */
+    CDCL_P_LEARNED_REPEAT_GT64,   /* the same, > 64 entries (the lane-0 bump) */
+    CDCL_P_LEARNED_LEN_64,
+    CDCL_P_LEARNED_LEN_65,
+    CDCL_P_RESOLVE_STEPS,         /* antecedent resolutions (REF.py:331-342) */
+    CDCL_P_RESOLVE_ALEN_MAX,      /* the longest antecedent resolved with */
+    CDCL_P_LEARNED_UNIT,
+    /* set tables, read around every watch-list add */
+    CDCL_P_TABLE_SLOTS_MAX,
+    CDCL_P_RESIZE_LE_4096,        /* resizes into <= 4,096 slots (register bitmap) */
+    CDCL_P_RESIZE_GT_4096,        /* resizes into more (lane 0) */
+    CDCL_P_RESIZE_USED_GT_50000,  /* resizes growing x2 */
+    CDCL_P_ADD_DUMMY_REUSE,
+    CDCL_P_ADD_MULTI_RUN,         /* adds that probed more than one run (perturbation) */
+    CDCL_P_ADD_SINGLE_SLOT,       /* adds with a single-slot run (i + 9 > mask) */
+    CDCL_P_ADD_SINGLE_SLOT_BIG,   /* the same in a table of more than 8 slots (where both forms occur) */
+    CDCL_P_ADD_PRESENT,           /* adds of a key already a member */
+    /* search */
+    CDCL_P_DECIDE_TIE,            /* decisions with >= 2 unassigned variables of the maximal activity */
+    CDCL_P_DECIDE_LOW_WORD,       /* the winner's double equals another candidate's in the high word only */
+    CDCL_NPATHS
+};
 
 typedef struct {
     /* formula (REF.py:221), grows by learned clauses (REF.py:349-350) */
@@ -45,7 +93,16 @@ typedef struct {
     pyset *kset;
     int32_t nk, capk;
     int32_t *kidx;       /* literal code -> key index + 1 (0 = absent) */
+    /* path counters (NULL: not counted) and their scratch */
+    int64_t *pc;
+    int64_t *slot, slotcap;   /* slots of a snapshot's members */
+    int64_t *seen, seencap;   /* clause -> last propagate pass that visited it */
+    int64_t pass;
 } cdcl_t;
+
+static inline void pc_max(cdcl_t *S, int i, int64_t x) {
+    if (S->pc[i] < x) S->pc[i] = x;
+}
 
 static inline int lcode(int32_t lit) { return (lit < 0 ? -lit : lit) * 2 + (lit < 0); }
 static inline int iabs(int32_t x) { return x < 0 ? -x : x; }
@@ -66,7 +123,28 @@ static int key_of(cdcl_t *S, int32_t lit, int create) {
 
 static void watch_add(cdcl_t *S, int32_t lit, int64_t idx) {
     const int k = key_of(S, lit, 1);
-    pyset_add_hashed(&S->kset[k], idx + 1, idx);
+    pyset *ws = &S->kset[k];
+    if (!S->pc) {
+        pyset_add_hashed(ws, idx + 1, idx);
+        return;
+    }
+    const int64_t mask = ws->mask, fill = ws->fill, used = ws->used;
+    int runs = 0, single = 0;
+    const int end = pyset_probe_runs(ws, idx + 1, idx, &runs, &single);
+    pyset_add_hashed(ws, idx + 1, idx);
+    S->pc[CDCL_P_ADD_MULTI_RUN] += runs > 1;
+    S->pc[CDCL_P_ADD_SINGLE_SLOT] += single > 0;
+    S->pc[CDCL_P_ADD_SINGLE_SLOT_BIG] += single > 0 && mask > PYSET_MINSIZE - 1;
+    S->pc[CDCL_P_ADD_PRESENT] += end == 2;
+    S->pc[CDCL_P_ADD_DUMMY_REUSE] += end == 1;
+    /* an add into an unused slot resizes at fill * 5 >= mask * 3, to 4 x (2 x
+     * beyond 50,000) the members, which is never the kept 8-slot table */
+    (void)used;
+    if (end == 0 && (fill + 1) * 5 >= mask * 3) {
+        S->pc[ws->mask + 1 <= 4096 ? CDCL_P_RESIZE_LE_4096 : CDCL_P_RESIZE_GT_4096] += 1;
+        S->pc[CDCL_P_RESIZE_USED_GT_50000] += ws->used > 50000;
+    }
+    pc_max(S, CDCL_P_TABLE_SLOTS_MAX, ws->mask + 1);
 }
 
 static void assign(cdcl_t *S, int v, int value, int32_t level, int64_t ante) {
@@ -106,7 +184,29 @@ static int propagate(cdcl_t *S, int64_t **snap, int64_t *snapcap, int32_t *unitb
     for (;;) {
         int32_t unit = 0;
         const int nk0 = S->nk;   /* list(self.watch_list): keys added during the pass are not visited */
+        /* counters: the kernel reads a 64-key batch's false tables as one stream
+         * (nothing a pass does changes which keys are false or their tables' sizes) */
+        int64_t excl[64];
+        int dup_pass = 0;
+        if (S->pc) {
+            ++S->pass;
+            if (S->seencap < S->capf) {
+                S->seen = (int64_t *)realloc(S->seen, sizeof(int64_t) * (size_t)S->capf);
+                memset(S->seen + S->seencap, 0, sizeof(int64_t) * (size_t)(S->capf - S->seencap));
+                S->seencap = S->capf;
+            }
+        }
         for (int ki = 0; ki < nk0; ++ki) {
+            if (S->pc && (ki & 63) == 0) {
+                int64_t run = 0;
+                for (int kk = ki; kk < nk0 && kk < ki + 64; ++kk) {
+                    const int32_t l2 = S->klit[kk];
+                    const int v2 = iabs(l2);
+                    excl[kk - ki] = run;
+                    if (S->val[v2] >= 0 && (l2 > 0) != S->val[v2]) run += S->kset[kk].mask + 1;
+                }
+                pc_max(S, CDCL_P_STREAM_LEN_MAX, run);
+            }
             const int32_t lit = S->klit[ki];
             const int v = iabs(lit);
             if (S->val[v] < 0 || (lit > 0) == S->val[v]) continue;
@@ -116,15 +216,37 @@ static int propagate(cdcl_t *S, int64_t **snap, int64_t *snapcap, int32_t *unitb
                 *snap = (int64_t *)realloc(*snap, sizeof(int64_t) * (size_t)*snapcap);
             }
             const int n = pyset_items(ws, *snap);   /* list(self.watch_list[lit]) */
+            if (S->pc) {
+                pc_max(S, CDCL_P_FALSE_KEY_INDEX_MAX, ki);
+                if (S->slotcap < *snapcap) {
+                    S->slotcap = *snapcap;
+                    S->slot = (int64_t *)realloc(S->slot, sizeof(int64_t) * (size_t)S->slotcap);
+                }
+                pyset_slots(ws, S->slot);
+            }
             for (int t = 0; t < n; ++t) {
                 const int64_t idx = (*snap)[t] - 1;
                 const cl_t *c = &S->f[idx];
                 int found = 0;
+                int64_t pos = 0;   /* the member's slot of the batch's stream */
+                if (S->pc) {
+                    pos = excl[ki & 63] + S->slot[t];
+                    S->pc[CDCL_P_STRADDLE_MEMBERS] += excl[ki & 63] / 256 < pos / 256;
+                    if (S->seen[idx] == S->pass && !dup_pass) {
+                        dup_pass = 1;
+                        S->pc[CDCL_P_DUP_VISIT_PASSES] += 1;
+                    }
+                    S->seen[idx] = S->pass;
+                }
                 for (int j = 0; j < c->len; ++j) {
                     const int32_t o = c->lits[j];
-                    if (o == lit) continue;
+                    if (o == lit) {
+                        if (S->pc && j >= 3) S->pc[CDCL_P_TAIL_SKIP_SELF] += 1;
+                        continue;
+                    }
                     const int ov = iabs(o);
                     if (S->val[ov] < 0 || (o > 0) == S->val[ov]) {
+                        if (S->pc) pc_max(S, CDCL_P_REPL_POS_MAX, j);
                         pyset_discard_hashed(&S->kset[ki], idx + 1, idx);
                         watch_add(S, o, idx);
                         ws = &S->kset[ki];   /* kset may have moved */
@@ -136,6 +258,11 @@ static int propagate(cdcl_t *S, int64_t **snap, int64_t *snapcap, int32_t *unitb
                     if (c->len == 1) {
                         unit = c->lits[0];
                     } else {
+                        if (S->pc) {
+                            pc_max(S, CDCL_P_CONFLICT_POS_MAX, pos);
+                            S->pc[CDCL_P_CONFLICT_LATER_CHUNK] += pos >= 64 && pos < 256;
+                            S->pc[CDCL_P_CONFLICT_LATER_WINDOW] += pos >= 256;
+                        }
                         *cl = c->lits;
                         *cn = c->len;
                         return 1;
@@ -187,7 +314,13 @@ static int in_list(const int32_t *a, int n, int32_t x) {
 
 /* REF.py:306-345.  Learned literals into *out (len *on), backtrack level into
  * *bt.  Returns -1 where the reference raises KeyError (an unassigned variable
- * in self.levels[...]). */
+ * in self.levels[...]).
+ * The resolution loop is never entered by the reference's own search: only the
+ * input's unit clauses set an antecedent (setup_watch_list), their variables
+ * sit at level 0, and the first maximal-level literal of a conflict on several
+ * levels is a decision.  CDCL_P_RESOLVE_STEPS is 0 over every path row, golden
+ * case and random batch (tests/test_cdcl_paths.py::
+ * test_antecedent_resolution_is_never_taken); the code stays as REF.py has it. */
 static int analyze_conflict(cdcl_t *S, const int32_t *conflict, int32_t cn, int32_t **out, int32_t *on,
                             int32_t *bt) {
     int32_t *lits = (int32_t *)malloc(sizeof(int32_t) * (size_t)(cn > 0 ? cn : 1));
@@ -201,17 +334,23 @@ static int analyze_conflict(cdcl_t *S, const int32_t *conflict, int32_t cn, int3
     }
     int second, distinct;
     int mx = level_max(S, lits, n, &second, &distinct);
+    if (S->pc) pc_max(S, CDCL_P_CONFLICT_LEN_MAX, cn);
     while (distinct > 1) {
         int32_t last = 0;
         for (int i = 0; i < n; ++i)
             if (S->lev[iabs(lits[i])] == mx) {
                 last = lits[i];
+                if (S->pc) pc_max(S, CDCL_P_MAXLEVEL_POS_MAX, i);
                 break;
             }
         if (last == 0) break;
         const int64_t a = S->ante[iabs(last)];
         if (a < 0) break;   /* None (absent) or -1 */
         const cl_t *ac = &S->f[a];
+        if (S->pc) {
+            S->pc[CDCL_P_RESOLVE_STEPS] += 1;
+            pc_max(S, CDCL_P_RESOLVE_ALEN_MAX, ac->len);
+        }
         int32_t *nl = (int32_t *)malloc(sizeof(int32_t) * (size_t)(n + ac->len + 1));
         int m = 0;
         for (int i = 0; i < n; ++i)
@@ -237,6 +376,17 @@ static int analyze_conflict(cdcl_t *S, const int32_t *conflict, int32_t cn, int3
 /* REF.py:347-357 */
 static void learn_clause(cdcl_t *S, const int32_t *c, int32_t n) {
     if (n == 0) return;
+    if (S->pc) {
+        int rep = 0;
+        for (int i = 0; i < n && !rep; ++i)
+            for (int j = 0; j < i; ++j)
+                if (iabs(c[j]) == iabs(c[i])) rep = 1;
+        if (rep) S->pc[n <= 64 ? CDCL_P_LEARNED_REPEAT_LE64 : CDCL_P_LEARNED_REPEAT_GT64] += 1;
+        pc_max(S, CDCL_P_LEARNED_LEN_MAX, n);
+        S->pc[CDCL_P_LEARNED_LEN_64] += n == 64;
+        S->pc[CDCL_P_LEARNED_LEN_65] += n == 65;
+        S->pc[CDCL_P_LEARNED_UNIT] += n == 1;
+    }
     const int64_t idx = S->nf;
     append_clause(S, c, n);
     if (n > 1) {
@@ -269,6 +419,19 @@ static int select_variable(cdcl_t *S) {
         }
     }
     if (best == 0) return 0;
+    if (S->pc) {   /* the kernel reduces the high word, the low word, then the index */
+        uint64_t wb, wv;
+        int tie = 0, low = 0;
+        memcpy(&wb, &bk, sizeof(wb));
+        for (int v = 1; v <= S->maxv; ++v) {
+            if (S->val[v] >= 0 || v == best) continue;
+            memcpy(&wv, &S->act[v], sizeof(wv));
+            tie |= wv == wb;
+            low |= wv != wb && (wv >> 32) == (wb >> 32);
+        }
+        S->pc[CDCL_P_DECIDE_TIE] += tie;
+        S->pc[CDCL_P_DECIDE_LOW_WORD] += low;
+    }
     S->var_inc *= S->var_decay;
     return best;
 }
@@ -283,10 +446,16 @@ static int select_variable(cdcl_t *S) {
  * stats[0..6] = solve-loop iterations, conflicts analysed, decisions, learned
  * clauses, final formula length, watch-list keys, decision level; *var_inc.
  */
-int oracle_cdcl(int nclauses, const int32_t *off, const int32_t *lits, int64_t max_iter, int32_t *model,
-                int32_t *model_len, int64_t *stats, double *var_inc) {
+static int cdcl_run(int nclauses, const int32_t *off, const int32_t *lits, int64_t max_iter, int32_t *model,
+                    int32_t *model_len, int64_t *stats, double *var_inc, int64_t *paths) {
     cdcl_t S;
     memset(&S, 0, sizeof(S));
+    S.pc = paths;
+    if (paths) {
+        memset(paths, 0, sizeof(int64_t) * CDCL_NPATHS);
+        paths[CDCL_P_FALSE_KEY_INDEX_MAX] = paths[CDCL_P_CONFLICT_POS_MAX] = paths[CDCL_P_REPL_POS_MAX] =
+            paths[CDCL_P_MAXLEVEL_POS_MAX] = -1;
+    }
     int maxv = 0;
     for (int64_t i = 0; i < (nclauses > 0 ? off[nclauses] : 0); ++i)
         if (iabs(lits[i]) > maxv) maxv = iabs(lits[i]);
@@ -383,6 +552,21 @@ int oracle_cdcl(int nclauses, const int32_t *off, const int32_t *lits, int64_t m
     free(S.lev);
     free(S.ante);
     free(S.act);
+    free(S.slot);
+    free(S.seen);
     free(snap);
     return result;
+}
+
+int oracle_cdcl(int nclauses, const int32_t *off, const int32_t *lits, int64_t max_iter, int32_t *model,
+                int32_t *model_len, int64_t *stats, double *var_inc) {
+    return cdcl_run(nclauses, off, lits, max_iter, model, model_len, stats, var_inc, NULL);
+}
+
+/* The same search; paths[0 .. npaths) receives the path counters (CDCL_P_*).
+ * Returns -3 if npaths is not this library's count (a stale caller or library). */
+int oracle_cdcl_paths(int nclauses, const int32_t *off, const int32_t *lits, int64_t max_iter, int32_t *model,
+                      int32_t *model_len, int64_t *stats, double *var_inc, int64_t *paths, int npaths) {
+    if (npaths != CDCL_NPATHS || !paths) return -3;
+    return cdcl_run(nclauses, off, lits, max_iter, model, model_len, stats, var_inc, paths);
 }

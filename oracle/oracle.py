@@ -23,12 +23,33 @@ def build():
     subprocess.run(["make", "-s", "-C", _HERE], check=True)
 
 
+def _rebuild():
+    subprocess.run(["make", "-s", "-B", "-C", _HERE], check=True)
+
+
+def _open(path=_LIB, rebuild=_rebuild):
+    """The library at `path`, rebuilt once if it predates an entry point this
+    module binds (a library kept from an older tree): never a silent pass."""
+    L = ctypes.CDLL(path)
+    if hasattr(L, "oracle_cdcl_paths"):
+        return L
+    import _ctypes
+    _ctypes.dlclose(L._handle)   # or the next CDLL returns the old mapping
+    del L
+    rebuild()
+    L = ctypes.CDLL(path)
+    if not hasattr(L, "oracle_cdcl_paths"):
+        _ctypes.dlclose(L._handle)
+        raise RuntimeError(f"{path} has no oracle_cdcl_paths after a rebuild: a stale oracle library")
+    return L
+
+
 def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(_LIB):
             build()
-        L = ctypes.CDLL(_LIB)
+        L = _open()
         P = ctypes.POINTER
         i32p, i64p = P(ctypes.c_int32), P(ctypes.c_int64)
         L.oracle_dpll.restype = ctypes.c_int
@@ -45,6 +66,8 @@ def lib():
         L.oracle_cdcl.restype = ctypes.c_int
         L.oracle_cdcl.argtypes = [ctypes.c_int, i32p, i32p, ctypes.c_int64, i32p, P(ctypes.c_int32), i64p,
                                   P(ctypes.c_double)]
+        L.oracle_cdcl_paths.restype = ctypes.c_int
+        L.oracle_cdcl_paths.argtypes = L.oracle_cdcl.argtypes + [i64p, ctypes.c_int]
         L.pyset_probe_from_list.restype = ctypes.c_int
         L.pyset_probe_from_list.argtypes = [i64p, ctypes.c_int, i64p]
         L.pyset_probe_resolvent.restype = ctypes.c_int
@@ -168,18 +191,43 @@ def pyset_var_pop(lists):
 CDCL_STATS = ("iterations", "conflicts", "decisions", "learned", "clauses", "watch_keys", "level")
 
 
-def cdcl(formula, max_iter=0):
+# The path counters of oracle_cdcl_paths, in the order of cdcl_oracle.c's
+# CDCL_P_* (which says what each counts): which code paths of csrc/cdcl.hip a
+# formula drives.  Maxima of a position are -1 where the event never happened.
+CDCL_PATHS = (
+    "false_key_index_max", "stream_len_max", "conflict_pos_max", "conflict_later_chunk",
+    "conflict_later_window", "straddle_members", "repl_pos_max",
+    "tail_skip_self", "dup_visit_passes",
+    "conflict_len_max", "learned_len_max", "maxlevel_pos_max", "learned_repeat_le64", "learned_repeat_gt64",
+    "learned_len_64", "learned_len_65", "resolve_steps", "resolve_alen_max", "learned_unit",
+    "table_slots_max", "resize_le_4096", "resize_gt_4096", "resize_used_gt_50000", "add_dummy_reuse",
+    "add_multi_run", "add_single_slot", "add_single_slot_big", "add_present",
+    "decide_tie", "decide_low_word")
+
+
+def cdcl(formula, max_iter=0, paths=False):
     """cdcl_solve (REF.py:382-384) restated: {"result": 1 True | 0 False | -1 the
     iteration cap | -2 the reference raises, "assignment": the assignment dict as
     signed literals in insertion order (the model for result 1), "var_inc",
-    "stats": CDCL_STATS}."""
+    "stats": CDCL_STATS}; with paths=True also "paths": CDCL_PATHS of the same
+    search."""
     off, lits = _csr(formula)
     nv = max([abs(l) for c in formula for l in c] + [1])
     model = np.zeros(nv + 1, dtype=np.int32)
     mlen = ctypes.c_int32(0)
     st = np.zeros(len(CDCL_STATS), dtype=np.int64)
     vi = ctypes.c_double(0.0)
-    r = lib().oracle_cdcl(len(formula), _p(off), _p(lits), int(max_iter), _p(model), ctypes.byref(mlen),
-                          _p(st, ctypes.c_int64), ctypes.byref(vi))
-    return {"result": r, "assignment": model[:mlen.value].tolist(), "var_inc": vi.value,
-            "stats": dict(zip(CDCL_STATS, st.tolist()))}
+    if paths:
+        pc = np.zeros(len(CDCL_PATHS), dtype=np.int64)
+        r = lib().oracle_cdcl_paths(len(formula), _p(off), _p(lits), int(max_iter), _p(model), ctypes.byref(mlen),
+                                    _p(st, ctypes.c_int64), ctypes.byref(vi), _p(pc, ctypes.c_int64), len(pc))
+        if r == -3:
+            raise RuntimeError("oracle_cdcl_paths: CDCL_PATHS does not match the library's counters")
+    else:
+        r = lib().oracle_cdcl(len(formula), _p(off), _p(lits), int(max_iter), _p(model), ctypes.byref(mlen),
+                              _p(st, ctypes.c_int64), ctypes.byref(vi))
+    out = {"result": r, "assignment": model[:mlen.value].tolist(), "var_inc": vi.value,
+           "stats": dict(zip(CDCL_STATS, st.tolist()))}
+    if paths:
+        out["paths"] = dict(zip(CDCL_PATHS, pc.tolist()))
+    return out

@@ -214,6 +214,34 @@ int pyset_items(const pyset *s, int64_t *out) {
     return n;
 }
 
+int pyset_slots(const pyset *s, int64_t *out) {
+    int n = 0;
+    for (int64_t k = 0; k <= s->mask; k++) {
+        const pyentry *e = &s->table[k];
+        if (e->key != 0 && e->key != PYSET_DUMMY) out[n++] = k;
+    }
+    return n;
+}
+
+int pyset_probe_runs(const pyset *s, int64_t key, int64_t hash, int *runs, int *single) {
+    uint64_t mask = (uint64_t)s->mask, i = (uint64_t)hash & mask, perturb = (uint64_t)hash;
+    int dummy = 0;
+    *runs = *single = 0;
+    for (;;) {
+        const int probes = i + LINEAR_PROBES <= mask ? LINEAR_PROBES : 0;
+        ++*runs;
+        *single += probes == 0;
+        for (int j = 0; j <= probes; j++) {
+            const pyentry *e = &s->table[i + (uint64_t)j];
+            if (e->key == 0) return dummy;
+            if (e->hash == hash && e->key == key) return 2;
+            if (e->hash == -1 && e->key == PYSET_DUMMY) dummy = 1;
+        }
+        perturb >>= PERTURB_SHIFT;
+        i = (i * 5 + 1 + perturb) & mask;
+    }
+}
+
 int64_t pyset_pop(pyset *s) {
     int64_t k = s->finger & s->mask;
     while (s->table[k].key == 0 || s->table[k].key == PYSET_DUMMY) {

@@ -44,6 +44,13 @@ void pyset_copy(pyset *dst, const pyset *src);    /* set_copy / make_new_set(src
 void pyset_difference(pyset *dst, const pyset *a, const pyset *b);   /* a - b  */
 void pyset_or(pyset *dst, const pyset *a, const pyset *b);           /* a | b  */
 int  pyset_items(const pyset *s, int64_t *out);   /* iteration order; returns count */
+int  pyset_slots(const pyset *s, int64_t *out);   /* the members' table slots, in iteration order */
+/* read-only: the walk pyset_add_hashed(s, key, hash) would make, as probe runs
+ * (a slot and the 9 after it where they fit before the table's end, else the
+ * slot alone): the runs read up to the one that ends the search, and how many
+ * of them were the single-slot form.  Returns how the add ends: 0 in an unused
+ * slot, 1 in a dummy passed on the way, 2 the key is a member already */
+int  pyset_probe_runs(const pyset *s, int64_t key, int64_t hash, int *runs, int *single);
 int64_t pyset_pop(pyset *s);                      /* set.pop()            */
 int  pyset_issuperset(const pyset *a, const pyset *b);
 

@@ -517,6 +517,12 @@ __device__ int64_t propagate(const CdclArgs &A, const St &S, Seq &q) {
 // not among the kept ones and not a repeat of an earlier antecedent literal
 // (a repeat is excluded exactly when its first occurrence was: same value,
 // same tests) -- every membership test runs on the lanes in parallel.
+// No search of the reference takes a resolution step: only the input's unit
+// clauses set an antecedent, their variables sit at level 0, and the first
+// maximal-level literal of a conflict on several levels is a decision.  The
+// oracle counts 0 steps over every path row, golden case and random batch
+// (tests/test_cdcl_paths.py::test_antecedent_resolution_is_never_taken), so
+// the loop below is kept as the reference has it and is pinned by reading only.
 __device__ int analyze_conflict(const St &S, int64_t conflict, int32_t cap, int32_t *bt) {
     const int ln = lane_id();
     const uint64_t lt = lanemask_lt();

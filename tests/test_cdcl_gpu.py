@@ -146,10 +146,11 @@ def test_cdcl_arena_form_beyond_lds():
 
 def test_cdcl_large_watch_tables():
     """Thousands of clauses watched by the same few literals: set tables grow
-    past the register occupancy bitmap of a resize (csrc/cdcl.hip
-    WS_BITMAP_SLOTS = 4,096 slots: beyond it the re-insertion probes memory),
-    collide along linear-probe runs and perturbation, and fill with dummies as
-    the watches move; against the oracle."""
+    to 2,048 slots (the oracle's path counters; tables past the register
+    occupancy bitmap of a resize, WS_BITMAP_SLOTS = 4,096, are the rows
+    resize_8192 / growth_x2 of tests/cdcl_paths.py), collide along linear-probe
+    runs and perturbation, and fill with dummies as the watches move; against
+    the oracle."""
     rng = random.Random(23)
     fs = []
     for n, m in ((10, 1500), (12, 2600), (8, 900), (14, 3200)):
