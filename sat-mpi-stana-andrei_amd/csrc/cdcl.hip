@@ -36,10 +36,10 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
-#include <mutex>
 #include <vector>
 
 #include "common.h"
+#include "host.h"
 
 namespace satmi {
 namespace {
@@ -935,60 +935,26 @@ bool make_cdcl_layout(int max_vars, int64_t max_clauses, int64_t max_lits, int m
 // Device memory of satmi_cdcl_batch_host, kept between calls (grow-only): the
 // per-wave arenas of a batch are sized for max_iter learned clauses and reach
 // gigabytes, whose hipMalloc / hipFree per call cost more than the solves of a
-// menu-sized batch.  One slot per concurrent call (a call takes a free slot of
-// its device or adds one, and returns it when done), each with its own
-// non-blocking stream: calls from several host threads overlap on the device,
-// so the waves a batch's few long solves leave idle run another batch.  The
-// slots are bounded by the peak number of concurrent calls; never destroyed (no
-// hipFree after the runtime's teardown).
+// menu-sized batch.  One slot per concurrent call, from the workspace pool
+// (host.h), each with its own non-blocking stream: calls from several host
+// threads overlap on the device, so the waves a batch's few long solves leave
+// idle run another batch.  A slot's memory carries nothing between calls, so a
+// failed call returns its slot like any other, and no slot is ever destroyed.
 struct CdclSlot {
     int dev = 0;
-    bool busy = false;
-    void *p = nullptr;
-    size_t cap = 0;
+    DevBuf mem;
     hipStream_t stream = nullptr;
-};
-struct CdclPool {
-    std::mutex mu;
-    std::vector<CdclSlot *> slots;
-};
-CdclPool &cdcl_pool() {
-    static CdclPool *c = new CdclPool;
-    return *c;
-}
-// a free slot of device `dev` (created with its stream when none is free)
-CdclSlot *cdcl_acquire(int dev) {
-    CdclPool &P = cdcl_pool();
-    std::lock_guard<std::mutex> lk(P.mu);
-    for (CdclSlot *c : P.slots)
-        if (c->dev == dev && !c->busy) {
-            c->busy = true;
-            return c;
-        }
-    CdclSlot *c = new CdclSlot;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete c;
-        return nullptr;
+    ~CdclSlot() {
+        if (stream) (void)hipStreamDestroy(stream);
     }
-    c->dev = dev;
-    c->busy = true;
-    P.slots.push_back(c);
-    return c;
-}
+    bool open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
+};
 // The calling thread's last satmi_cdcl_batch_host launch (satmi_cdcl_last_stats).
 struct CdclStats {
     double span_s = 0.0, busy_wave_s = 0.0;
     int resident_waves = 0;
 };
 thread_local CdclStats g_cdcl_stats;
-
-struct CdclSlotGuard {
-    CdclSlot *c;
-    ~CdclSlotGuard() {
-        std::lock_guard<std::mutex> lk(cdcl_pool().mu);
-        c->busy = false;
-    }
-};
 
 }  // namespace
 }  // namespace satmi
@@ -1044,9 +1010,10 @@ extern "C" int satmi_cdcl_batch_host(int num_instances, const int32_t *h_inst_cl
         set_error("satmi_cdcl_batch_host: instance too large");
         return SATMI_ERR_TOO_LARGE;
     }
-    int dev = 0, cus = 256;
-    SATMI_HIP(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    int dev = 0;
+    DeviceFacts facts;
+    SATMI_TRY(device_facts(&facts, &dev));
+    const double ticks_per_s = facts.ticks_per_s;
     size_t free_b = 0, total_b = 0;
     SATMI_HIP(hipMemGetInfo(&free_b, &total_b));
     const size_t by_mem = (free_b / 2) / std::max<uint64_t>(lay.bytes, 1);
@@ -1054,11 +1021,7 @@ extern "C" int satmi_cdcl_batch_host(int num_instances, const int32_t *h_inst_cl
         set_error("satmi_cdcl_batch_host: one instance's arena exceeds half the free device memory");
         return SATMI_ERR_NOMEM;
     }
-    const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)cus * 32, by_mem});
-    int wclock = 0;
-    double ticks_per_s = 1e8;
-    if (hipDeviceGetAttribute(&wclock, hipDeviceAttributeWallClockRate, dev) == hipSuccess && wclock > 0)
-        ticks_per_s = (double)wclock * 1000.0;
+    const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)facts.cus * 32, by_mem});
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t o_icb = 0, o_clb = o_icb + up(4 * (size_t)(num_instances + 1));
     const size_t o_lits = o_clb + up(4 * (size_t)(C + 1));
@@ -1071,23 +1034,15 @@ extern "C" int satmi_cdcl_batch_host(int num_instances, const int32_t *h_inst_cl
     const size_t o_wc = o_vi + up(8 * (size_t)num_instances);
     const size_t o_arena = o_wc + 256;
     const size_t total = o_arena + (size_t)grid * (size_t)lay.bytes;
-    CdclSlot *slot = cdcl_acquire(dev);
-    if (!slot) {
+    Lease<CdclSlot> lease{Pool<CdclSlot>::get().acquire(dev)};
+    if (!lease.w) {
         set_error("satmi_cdcl_batch_host: hipStreamCreate failed");
         return SATMI_ERR_HIP;
     }
-    CdclSlotGuard guard{slot};
-    if (slot->cap < total) {
-        if (slot->p) (void)hipFree(slot->p);
-        slot->p = nullptr;
-        slot->cap = 0;
-        void *p = nullptr;
-        SATMI_HIP(hipMalloc(&p, total));
-        slot->p = p;
-        slot->cap = total;
-    }
-    unsigned char *d = (unsigned char *)slot->p;
-    hipStream_t s = slot->stream;
+    lease.ok = true;   // whatever the call's outcome (see CdclSlot)
+    SATMI_TRY(lease.w->mem.reserve(total));
+    unsigned char *d = lease.w->mem.as<unsigned char>();
+    hipStream_t s = lease.w->stream;
     int rc = SATMI_OK;
     do {
         auto h2d = [&](size_t off, const void *src, size_t bytes) {

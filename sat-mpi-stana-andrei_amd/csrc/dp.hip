@@ -54,11 +54,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <type_traits>
 #include <vector>
 
 #include "common.h"
+#include "host.h"
 #include "prims.h"
 #include "pyset_dev.h"
 
@@ -1591,56 +1591,18 @@ __global__ void __launch_bounds__(64 * ASM_WAVES) dp_assemble_kernel(DpArgs A) {
 // ------------------------------------------------------------------ host side
 namespace {
 
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-    Buf() = default;
-    Buf(const Buf &) = delete;
-    // grow to >= bytes; keep the first `keep` bytes (stream-ordered copy); `fill`
-    // (>= 0) initialises the whole new buffer first
-    int need(size_t bytes, hipStream_t s = nullptr, size_t keep = 0, int fill = -1) {
-        if (bytes <= cap) return SATMI_OK;
-        const size_t want = std::max<size_t>(bytes + bytes / 2, 256);
-        void *np = nullptr;
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b) {
-            set_error("satmi_dp_host: out of device memory (" + std::to_string(want >> 20) + " MiB wanted, " +
-                      std::to_string(free_b >> 20) + " MiB free); bound the elimination with clause_limit");
-            return SATMI_ERR_NOMEM;
-        }
-        SATMI_HIP(hipMalloc(&np, want));
-        if (fill >= 0) SATMI_HIP(hipMemsetAsync(np, fill, want, s));
-        if (p && keep) SATMI_HIP(hipMemcpyAsync(np, p, std::min(keep, cap), hipMemcpyDeviceToDevice, s));
-        if (p) {
-            SATMI_HIP(hipStreamSynchronize(s));   // the old buffer is no longer read
-            (void)hipFree(p);
-        }
-        p = np;
-        cap = want;
-        return SATMI_OK;
-    }
-    template <class T>
-    T *as() const { return (T *)p; }
-};
-
-#define DP_TRY(x)                        \
-    do {                                 \
-        int _rc = (x);                   \
-        if (_rc != SATMI_OK) return _rc; \
-    } while (0)
+// The buffers grow step by step with the elimination (DevBuf::grow).
+constexpr OomText DP_OOM{"satmi_dp_host", "bound the elimination with clause_limit"};
 
 struct Gen {   // one generation's per-clause arrays
-    Buf off, mask, fill, used, bits;
+    DevBuf off, mask, fill, used, bits;
     int reserve(int64_t n, int K, hipStream_t s, int64_t keep_n) {
         n = std::max<int64_t>(n, 1);
-        DP_TRY(off.need(8 * (size_t)n, s, 8 * (size_t)keep_n));
-        DP_TRY(mask.need(4 * (size_t)n, s, 4 * (size_t)keep_n));
-        DP_TRY(fill.need(4 * (size_t)n, s, 4 * (size_t)keep_n));
-        DP_TRY(used.need(4 * (size_t)n, s, 4 * (size_t)keep_n));
-        DP_TRY(bits.need(8 * (size_t)n * K, s, 8 * (size_t)keep_n * K));
+        SATMI_TRY(off.grow(8 * (size_t)n, s, &DP_OOM, 8 * (size_t)keep_n));
+        SATMI_TRY(mask.grow(4 * (size_t)n, s, &DP_OOM, 4 * (size_t)keep_n));
+        SATMI_TRY(fill.grow(4 * (size_t)n, s, &DP_OOM, 4 * (size_t)keep_n));
+        SATMI_TRY(used.grow(4 * (size_t)n, s, &DP_OOM, 4 * (size_t)keep_n));
+        SATMI_TRY(bits.grow(8 * (size_t)n * K, s, &DP_OOM, 8 * (size_t)keep_n * K));
         return SATMI_OK;
     }
     ClauseList view() const {
@@ -1669,14 +1631,13 @@ struct DpGraph {
     }
 };
 
-// Device buffers of one solve, kept between calls (grow-only) in a process-wide
-// pool: a call takes a free workspace (or makes one) and returns it when done,
-// so concurrent calls from any number of threads each own one and the number
-// of workspaces is the peak number of concurrent calls.
+// Device buffers of one solve, kept between calls (grow-only) in the workspace
+// pool (host.h).  A call that failed part-way destroys its workspace: its
+// device state -- epoch stamps, the hash table -- may not be clean.
 struct DpWork {
-    Buf d_off, d_lits, d_v2d, d_d2v, state, firstpos, order, popscratch, trace;
-    Buf plist, nlist, rlist, rbits, ntbits, table, uslot, dropped, hit, surv, klist, keptbits, xs, arena;
-    Buf rkeys, skeys, ustage, stripes;
+    DevBuf d_off, d_lits, d_v2d, d_d2v, state, firstpos, order, popscratch, trace;
+    DevBuf plist, nlist, rlist, rbits, ntbits, table, uslot, dropped, hit, surv, klist, keptbits, xs, arena;
+    DevBuf rkeys, skeys, ustage, stripes;
     Gen g[2];
     int64_t ncl_cap = 0, pair_cap = 0, arena_cap = 0, xs_cap = 0;
     uint64_t tslots = 0;
@@ -1695,55 +1656,9 @@ struct DpWork {
         if (stream) (void)hipStreamDestroy(stream);
         if (pin) (void)hipHostFree(pin);
     }
-};
-
-struct DpPool {
-    std::mutex mu;
-    std::vector<DpWork *> free_list;
-};
-DpPool &dp_pool() {
-    static DpPool *p = new DpPool;   // never destroyed: no hipFree after the runtime's teardown
-    return *p;
-}
-DpWork *dp_acquire(int dev) {
-    DpPool &P = dp_pool();
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        for (size_t i = 0; i < P.free_list.size(); ++i)
-            if (P.free_list[i]->dev == dev) {
-                DpWork *w = P.free_list[i];
-                P.free_list.erase(P.free_list.begin() + (long)i);
-                return w;
-            }
-    }
-    DpWork *w = new DpWork;
-    w->dev = dev;
-    if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void **)&w->pin, sizeof(DpState), hipHostMallocDefault) != hipSuccess) {
-        delete w;
-        return nullptr;
-    }
-    return w;
-}
-void dp_release(DpWork *w) {
-    DpPool &P = dp_pool();
-    std::lock_guard<std::mutex> g(P.mu);
-    P.free_list.push_back(w);
-}
-// A call's hold on a workspace: returned to the pool after a call that
-// completed; destroyed after a call that failed part-way (its device state --
-// epoch stamps, the hash table -- may not be clean).
-struct DpLease {
-    DpWork *w;
-    bool ok = false;
-    ~DpLease() {
-        if (!w) return;
-        if (ok) {
-            dp_release(w);
-        } else {
-            (void)hipStreamSynchronize(w->stream);
-            delete w;
-        }
+    bool open() {
+        return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
+               hipHostMalloc((void **)&pin, sizeof(DpState), hipHostMallocDefault) == hipSuccess;
     }
 };
 
@@ -1757,19 +1672,19 @@ int grow_pairs(DpWork &W, int64_t npairs, int K) {
         return SATMI_ERR_TOO_LARGE;
     }
     hipStream_t s = W.stream;
-    DP_TRY(W.rbits.need(8 * (size_t)cap * K, s));
-    DP_TRY(W.ntbits.need(8 * (size_t)((cap + 63) / 64 + 1), s));
-    DP_TRY(W.uslot.need(4 * (size_t)cap, s));
-    DP_TRY(W.surv.need(4 * (size_t)cap, s));
-    DP_TRY(W.klist.need(4 * (size_t)cap, s));
-    DP_TRY(W.ustage.need(4 * (size_t)DP_STRIPES * cap, s));
-    DP_TRY(W.skeys.need(8 * (size_t)cap * K, s));
-    DP_TRY(W.dropped.need(4 * (size_t)cap, s, 0, 0));
-    DP_TRY(W.hit.need(4 * (size_t)cap, s, 0, 0));
-    DP_TRY(W.keptbits.need(4 * (size_t)((cap + 31) / 32 + 1), s, 0, 0));
+    SATMI_TRY(W.rbits.grow(8 * (size_t)cap * K, s, &DP_OOM));
+    SATMI_TRY(W.ntbits.grow(8 * (size_t)((cap + 63) / 64 + 1), s, &DP_OOM));
+    SATMI_TRY(W.uslot.grow(4 * (size_t)cap, s, &DP_OOM));
+    SATMI_TRY(W.surv.grow(4 * (size_t)cap, s, &DP_OOM));
+    SATMI_TRY(W.klist.grow(4 * (size_t)cap, s, &DP_OOM));
+    SATMI_TRY(W.ustage.grow(4 * (size_t)DP_STRIPES * cap, s, &DP_OOM));
+    SATMI_TRY(W.skeys.grow(8 * (size_t)cap * K, s, &DP_OOM));
+    SATMI_TRY(W.dropped.grow(4 * (size_t)cap, s, &DP_OOM, 0, 0));
+    SATMI_TRY(W.hit.grow(4 * (size_t)cap, s, &DP_OOM, 0, 0));
+    SATMI_TRY(W.keptbits.grow(4 * (size_t)((cap + 31) / 32 + 1), s, &DP_OOM, 0, 0));
     uint64_t ts = 1024;
     while (ts < 2 * (uint64_t)cap) ts <<= 1;
-    DP_TRY(W.table.need(8 * (size_t)ts, s, 0, 0xFF));
+    SATMI_TRY(W.table.grow(8 * (size_t)ts, s, &DP_OOM, 0, 0xFF));
     // a buffer that did not move keeps its contents: the stamps stay below
     // the next epoch, every step leaves the bitmap and the table clear (slots
     // past the old table size were never used)
@@ -1789,12 +1704,12 @@ int grow_ncl(DpWork &W, int64_t n, int K, int cur, int64_t keep_n) {
     if (n <= W.ncl_cap && W.K == K) return SATMI_OK;
     hipStream_t s = W.stream;
     const int64_t cap = std::max<int64_t>(n + n / 2, 1024);
-    DP_TRY(W.g[cur].reserve(cap, K, s, keep_n));
-    DP_TRY(W.g[cur ^ 1].reserve(cap, K, s, 0));
-    DP_TRY(W.plist.need(8 * (size_t)cap, s));
-    DP_TRY(W.nlist.need(8 * (size_t)cap, s));
-    DP_TRY(W.rlist.need(8 * (size_t)cap, s));
-    DP_TRY(W.rkeys.need(8 * (size_t)cap * K, s));
+    SATMI_TRY(W.g[cur].reserve(cap, K, s, keep_n));
+    SATMI_TRY(W.g[cur ^ 1].reserve(cap, K, s, 0));
+    SATMI_TRY(W.plist.grow(8 * (size_t)cap, s, &DP_OOM));
+    SATMI_TRY(W.nlist.grow(8 * (size_t)cap, s, &DP_OOM));
+    SATMI_TRY(W.rlist.grow(8 * (size_t)cap, s, &DP_OOM));
+    SATMI_TRY(W.rkeys.grow(8 * (size_t)cap * K, s, &DP_OOM));
     int64_t c = INT64_MAX;
     for (int g = 0; g < 2; ++g) {
         c = std::min<int64_t>(c, (int64_t)(W.g[g].off.cap / 8));
@@ -1832,20 +1747,8 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
     const int64_t Ltot = nclauses > 0 ? h_clause_off[nclauses] : 0;
     int maxvar = 0, maxlen = 0;
     for (int c = 0; c < nclauses; ++c) maxlen = std::max(maxlen, h_clause_off[c + 1] - h_clause_off[c]);
-    for (int64_t i = 0; i < Ltot; ++i) {
-        if (h_lits[i] == 0 || h_lits[i] == INT32_MIN) {
-            set_error("satmi_dp_host: literal 0 / INT32_MIN");
-            return SATMI_ERR_ARG;
-        }
-        maxvar = std::max(maxvar, std::abs(h_lits[i]));
-    }
-    std::vector<int32_t> var2dense(maxvar + 1, -1), dense2var;
-    for (int64_t i = 0; i < Ltot; ++i) var2dense[std::abs(h_lits[i])] = 1;
-    for (int v = 1; v <= maxvar; ++v)
-        if (var2dense[v] >= 0) {
-            var2dense[v] = (int32_t)dense2var.size();
-            dense2var.push_back(v);
-        }
+    std::vector<int32_t> var2dense, dense2var;
+    SATMI_TRY(dense_var_index("satmi_dp_host", h_lits, Ltot, &maxvar, &var2dense, &dense2var));
     const int V = (int)dense2var.size();
     g_dp_stats = DpStats{};
     if (V == 0) {   // no variables: `while variables` never runs -- True (REF.py:130)
@@ -1856,8 +1759,10 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
     const int K = 2 * Wd;
     g_dp_stats.words = K;
     int dev_id = 0;
-    SATMI_HIP(hipGetDevice(&dev_id));
-    DpLease lease{dp_acquire(dev_id)};
+    DeviceFacts dev;
+    SATMI_TRY(device_facts(&dev, &dev_id));
+    const double hz = dev.ticks_per_s;
+    Lease<DpWork> lease{Pool<DpWork>::get().acquire(dev_id)};
     if (!lease.w) {
         set_error("satmi_dp_host: hipStreamCreate failed");
         return SATMI_ERR_HIP;
@@ -1869,23 +1774,23 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
         Wk.pair_cap = 0;
     }
     const int64_t cap0 = cap_for(maxlen);
-    DP_TRY(Wk.d_off.need(4 * (size_t)(nclauses + 1), s));
-    DP_TRY(Wk.d_lits.need(4 * (size_t)std::max<int64_t>(Ltot, 1), s));
-    DP_TRY(Wk.d_v2d.need(4 * (size_t)(maxvar + 1), s));
-    DP_TRY(Wk.d_d2v.need(4 * (size_t)V, s));
-    DP_TRY(Wk.state.need(sizeof(DpState), s));
-    DP_TRY(Wk.firstpos.need(8 * (size_t)V, s));
-    DP_TRY(Wk.order.need(4 * (size_t)V, s));
+    SATMI_TRY(Wk.d_off.grow(4 * (size_t)(nclauses + 1), s, &DP_OOM));
+    SATMI_TRY(Wk.d_lits.grow(4 * (size_t)std::max<int64_t>(Ltot, 1), s, &DP_OOM));
+    SATMI_TRY(Wk.d_v2d.grow(4 * (size_t)(maxvar + 1), s, &DP_OOM));
+    SATMI_TRY(Wk.d_d2v.grow(4 * (size_t)V, s, &DP_OOM));
+    SATMI_TRY(Wk.state.grow(sizeof(DpState), s, &DP_OOM));
+    SATMI_TRY(Wk.firstpos.grow(8 * (size_t)V, s, &DP_OOM));
+    SATMI_TRY(Wk.order.grow(4 * (size_t)V, s, &DP_OOM));
     const int64_t popcap = cap_for(V);
-    DP_TRY(Wk.popscratch.need(4 * (size_t)2 * popcap, s));
-    DP_TRY(Wk.trace.need(4 * (size_t)(V + 1), s));
-    DP_TRY(Wk.stripes.need(8 * 3 * DP_STRIPES, s, 0, 0));
-    DP_TRY(grow_ncl(Wk, std::max<int64_t>(nclauses, 1), K, 0, 0));
-    DP_TRY(grow_pairs(Wk, 1, K));
+    SATMI_TRY(Wk.popscratch.grow(4 * (size_t)2 * popcap, s, &DP_OOM));
+    SATMI_TRY(Wk.trace.grow(4 * (size_t)(V + 1), s, &DP_OOM));
+    SATMI_TRY(Wk.stripes.grow(8 * 3 * DP_STRIPES, s, &DP_OOM, 0, 0));
+    SATMI_TRY(grow_ncl(Wk, std::max<int64_t>(nclauses, 1), K, 0, 0));
+    SATMI_TRY(grow_pairs(Wk, 1, K));
     const int64_t arena0 = (int64_t)nclauses * 2 * cap0;
-    DP_TRY(Wk.arena.need(4 * (size_t)std::max<int64_t>(arena0 * 4, 1 << 16), s));
+    SATMI_TRY(Wk.arena.grow(4 * (size_t)std::max<int64_t>(arena0 * 4, 1 << 16), s, &DP_OOM));
     Wk.arena_cap = (int64_t)(Wk.arena.cap / 4);
-    DP_TRY(Wk.xs.need(4 * (size_t)(1 << 16), s));
+    SATMI_TRY(Wk.xs.grow(4 * (size_t)(1 << 16), s, &DP_OOM));
     Wk.xs_cap = (int64_t)(Wk.xs.cap / 4);
 
     if (nclauses > 0) {
@@ -1903,8 +1808,6 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
     st.epoch = Wk.epoch;
     SATMI_HIP(hipMemcpyAsync(Wk.state.p, Wk.pin, sizeof(DpState), hipMemcpyHostToDevice, s));
 
-    double hz = 1e8;
-    (void)satmi_wallclock_hz(&hz);
     const bool record = h_rec_lits && h_rec_clause_off && h_rec_step_off;
     const char *inl_env = std::getenv("SATMI_DP_INLINE");
     const bool inline_on = inl_env && inl_env[0] == '1';
@@ -2052,7 +1955,7 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
                 G.args = A;
                 G.batch = batch;
             }
-            for (int k = 0; k < batch; ++k) DP_TRY(enqueue_step(A));
+            for (int k = 0; k < batch; ++k) SATMI_TRY(enqueue_step(A));
         }
         SATMI_HIP(hipEventRecord(ev[1], s));
         enqueued += batch;
@@ -2065,14 +1968,14 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
         }
         if (st.overflow) {   // grow what ran out, then run the step again
             const int cur = st.cur;
-            if (st.overflow & OVF_PAIRS) DP_TRY(grow_pairs(Wk, st.need[0], K));
-            if (st.overflow & OVF_NCL) DP_TRY(grow_ncl(Wk, st.need[1], K, cur, st.ncl));
+            if (st.overflow & OVF_PAIRS) SATMI_TRY(grow_pairs(Wk, st.need[0], K));
+            if (st.overflow & OVF_NCL) SATMI_TRY(grow_ncl(Wk, st.need[1], K, cur, st.ncl));
             if (st.overflow & OVF_ARENA) {
-                DP_TRY(Wk.arena.need(4 * (size_t)st.need[2], s, 4 * (size_t)st.arena_top));
+                SATMI_TRY(Wk.arena.grow(4 * (size_t)st.need[2], s, &DP_OOM, 4 * (size_t)st.arena_top));
                 Wk.arena_cap = (int64_t)(Wk.arena.cap / 4);
             }
             if (st.overflow & OVF_XS) {
-                DP_TRY(Wk.xs.need(4 * (size_t)st.need[3], s));
+                SATMI_TRY(Wk.xs.grow(4 * (size_t)st.need[3], s, &DP_OOM));
                 Wk.xs_cap = (int64_t)(Wk.xs.cap / 4);
             }
             st.overflow = 0;
@@ -2161,15 +2064,6 @@ extern "C" int satmi_dp_last_stats(int64_t *steps, int64_t *subset_tests, int64_
 // Free every idle workspace of this solver (device buffers, streams, pinned
 // words); calls in flight keep theirs.  The next call allocates afresh.
 extern "C" int satmi_dp_trim(void) {
-    std::vector<DpWork *> idle;
-    {
-        auto &P = dp_pool();
-        std::lock_guard<std::mutex> g(P.mu);
-        idle.swap(P.free_list);
-    }
-    for (DpWork *w : idle) {
-        (void)hipStreamSynchronize(w->stream);
-        delete w;
-    }
+    Pool<DpWork>::get().trim();
     return SATMI_OK;
 }

@@ -42,12 +42,13 @@
 #include <climits>
 #include <cstdio>
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "common.h"
+#include "host.h"
 #include "dpll_scan.h"
 
 namespace satmi {
@@ -994,47 +995,65 @@ static bool make_wide_layout(int max_vars, int max_clauses, int max_lits, DpllLa
     return true;
 }
 
-// Per-device launch state.  Each stream gets its own work counter, so batches
-// launched on different streams (a pipelined caller overlapping one batch's
-// tail with the next batch) never share a queue; launches on one stream are
-// ordered, so reusing that stream's counter is safe.
-struct DeviceWork {
-    std::unordered_map<hipStream_t, uint32_t *> counters;
-    // incremental scan kernel: occurrence-list scratch per stream (grown, never shrunk)
-    std::unordered_map<hipStream_t, std::pair<uint16_t *, size_t>> occ;
-    // branch splitting: slot pool + donation stacks per stream (grown, never
-    // shrunk) and the stream's launch tag for the slot states
-    std::unordered_map<hipStream_t, std::pair<void *, size_t>> split;
-    std::unordered_map<hipStream_t, uint32_t> split_epoch;
-    std::unordered_map<hipStream_t, bool> split_last;   // the stream's last DPLL launch split (stats valid)
-    // wide general kernel: per-wave HBM arenas per stream (grown, never shrunk)
-    std::unordered_map<hipStream_t, std::pair<void *, size_t>> arena;
-    double ticks_per_s = 1e8;
-    bool init = false;
-};
-static std::mutex g_work_mu;
-static std::vector<DeviceWork> g_work;
+// The launch state of every (device, stream) that ran a DPLL batch (DpllStream,
+// host.h).  The mutex guards the map only: a stream's state is used by the
+// caller launching on that stream.  Never destroyed: no hipFree after the
+// runtime's teardown.
+static std::mutex g_streams_mu;
+static auto &g_streams = *new std::map<std::pair<int, hipStream_t>, DpllStream>;
 static std::atomic<int> g_kernel_policy{SATMI_KERNEL_AUTO};
 static std::atomic<int> g_split_enable{1};
 static std::atomic<int> g_split_helpers{SPLIT_HELPERS_PER_CU};
 static std::atomic<int> g_split_warmup{SPLIT_WARMUP_NODES};
 
-static int device_work(hipStream_t stream, DeviceWork **out, uint32_t **counter) {
+// The state of `stream` on the current device: made with its work counter when
+// the stream has none and `create` is set, else *out = nullptr.
+static int dpll_stream(hipStream_t stream, bool create, DpllStream **out) {
     int dev = 0;
     SATMI_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_work_mu);
-    if ((int)g_work.size() <= dev) g_work.resize(dev + 1);
-    DeviceWork &w = g_work[dev];
-    if (!w.init) {
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0)
-            w.ticks_per_s = (double)khz * 1000.0;
-        w.init = true;
+    std::lock_guard<std::mutex> lk(g_streams_mu);
+    *out = nullptr;
+    auto it = g_streams.find({dev, stream});
+    if (it == g_streams.end()) {
+        if (!create) return SATMI_OK;
+        it = g_streams.try_emplace({dev, stream}).first;
+        it->second.stream = stream;
     }
-    uint32_t *&c = w.counters[stream];
-    if (!c) SATMI_HIP(hipMalloc(&c, 256));
-    *out = &w;
-    *counter = c;
+    DpllStream &st = it->second;
+    if (create && !st.counter) SATMI_HIP(hipMalloc(&st.counter, 256));
+    *out = &st;
+    return SATMI_OK;
+}
+
+// The workgroup shape of dpll_batch_kernel that keeps the most waves resident
+// under LDS (<= 32 waves and, conservatively, <= 16 workgroups per CU);
+// waves_per_cu = 0: no shape fits.
+struct NarrowShape {
+    int waves_per_wg = 1, wg_per_cu = 1, waves_per_cu = 0;
+};
+static NarrowShape narrow_shape(uint32_t lds_bytes_per_wave) {
+    NarrowShape S;
+    for (int wpg : {4, 2, 1}) {
+        const int wgs = std::min(16, (int)((160u * 1024u) / (lds_bytes_per_wave * (uint32_t)wpg)));
+        const int waves = std::min(32, wgs * wpg);
+        if (wgs >= 1 && waves > S.waves_per_cu) {
+            S.waves_per_cu = waves;
+            S.waves_per_wg = wpg;
+            S.wg_per_cu = std::max(1, std::min(wgs, 32 / wpg));
+        }
+    }
+    return S;
+}
+
+// A host copy of the splitting scratch head of the stream's last DPLL launch;
+// *split = false (and no copy) when that launch did not split.
+static int split_head(hipStream_t stream, unsigned char head[SPLIT_HEAD_BYTES], bool *split) {
+    DpllStream *st = nullptr;
+    SATMI_TRY(dpll_stream(stream, false, &st));
+    *split = st && st->split_last && st->split.p;
+    if (!*split) return SATMI_OK;
+    SATMI_HIP(hipStreamSynchronize(stream));
+    SATMI_HIP(hipMemcpy(head, st->split.p, SPLIT_HEAD_BYTES, hipMemcpyDeviceToHost));
     return SATMI_OK;
 }
 
@@ -1047,11 +1066,9 @@ extern "C" int satmi_dpll_launch_span(void *stream, uint64_t *d_span) {
         set_error("satmi_dpll_launch_span: d_span is NULL");
         return SATMI_ERR_ARG;
     }
-    DeviceWork *w = nullptr;
-    uint32_t *wc = nullptr;
-    int rc = device_work((hipStream_t)stream, &w, &wc);
-    if (rc) return rc;
-    SATMI_HIP(hipMemcpyAsync(d_span, (uint64_t *)wc + 1, 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice,
+    DpllStream *st = nullptr;
+    SATMI_TRY(dpll_stream((hipStream_t)stream, true, &st));
+    SATMI_HIP(hipMemcpyAsync(d_span, (uint64_t *)st->counter + 1, 2 * sizeof(uint64_t), hipMemcpyDeviceToDevice,
                              (hipStream_t)stream));
     return SATMI_OK;
 }
@@ -1061,98 +1078,10 @@ extern "C" int satmi_wallclock_hz(double *hz) {
         set_error("satmi_wallclock_hz: hz is NULL");
         return SATMI_ERR_ARG;
     }
-    DeviceWork *w = nullptr;
-    uint32_t *wc = nullptr;
-    int rc = device_work(nullptr, &w, &wc);
-    if (rc) return rc;
-    *hz = w->ticks_per_s;
+    DeviceFacts dev;
+    SATMI_TRY(device_facts(&dev));
+    *hz = dev.ticks_per_s;
     return SATMI_OK;
-}
-
-// Occurrence-list scratch of the incremental kernel on `stream`: launches on one
-// stream are ordered, so a buffer is only replaced after the stream drained.
-static uint16_t *occ_scratch(hipStream_t stream, size_t bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_work_mu);
-    if ((int)g_work.size() <= dev) g_work.resize(dev + 1);
-    auto &slot = g_work[dev].occ[stream];
-    if (slot.second >= bytes) return slot.first;
-    if (slot.first) {
-        if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-        (void)hipFree(slot.first);
-        slot = {nullptr, 0};
-    }
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        set_error("occurrence-list scratch: hipMalloc failed");
-        return nullptr;
-    }
-    slot = {(uint16_t *)p, bytes};
-    return slot.first;
-}
-
-// Per-wave arenas of the wide general kernel on `stream` (same lifetime rule).
-static void *arena_scratch(hipStream_t stream, size_t bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_work_mu);
-    if ((int)g_work.size() <= dev) g_work.resize(dev + 1);
-    auto &slot = g_work[dev].arena[stream];
-    if (slot.second >= bytes) return slot.first;
-    if (slot.first) {
-        if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-        (void)hipFree(slot.first);
-        slot = {nullptr, 0};
-    }
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        set_error("wide DPLL arenas: hipMalloc failed");
-        return nullptr;
-    }
-    slot = {p, bytes};
-    return slot.first;
-}
-
-// Branch-splitting scratch on `stream` (same lifetime rule as occ_scratch) and
-// the next launch tag of its slot states.
-static void *split_scratch(hipStream_t stream, size_t bytes, uint32_t *epoch) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(g_work_mu);
-    if ((int)g_work.size() <= dev) g_work.resize(dev + 1);
-    auto &slot = g_work[dev].split[stream];
-    uint32_t &ep = g_work[dev].split_epoch[stream];
-    if (slot.second < bytes) {
-        if (slot.first) {
-            if (hipStreamSynchronize(stream) != hipSuccess) return nullptr;
-            (void)hipFree(slot.first);
-            slot = {nullptr, 0};
-        }
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) {
-            set_error("branch-splitting scratch: hipMalloc failed");
-            return nullptr;
-        }
-        // fresh memory: no stale state may carry the next tags
-        if (hipMemsetAsync(p, 0, bytes, stream) != hipSuccess) return nullptr;
-        slot = {p, bytes};
-    }
-    ep = (ep + 1u) & 0x0FFFFFFFu;
-    if (ep == 0u) ep = 1u;
-    *epoch = ep;
-    g_work[dev].split_last[stream] = true;
-    return slot.first;
-}
-
-// A DPLL launch on `stream` is about to be made: until its split_scratch call
-// (only launches that split make one) the stream has no split statistics.
-static void split_mark_unsplit(hipStream_t stream) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_work_mu);
-    if ((int)g_work.size() <= dev) g_work.resize(dev + 1);
-    g_work[dev].split_last[stream] = false;
 }
 
 extern "C" int satmi_dpll_split_stats(void *stream, int64_t *out) {
@@ -1160,24 +1089,11 @@ extern "C" int satmi_dpll_split_stats(void *stream, int64_t *out) {
         set_error("satmi_dpll_split_stats: out is NULL");
         return SATMI_ERR_ARG;
     }
-    for (int i = 0; i < 7; ++i) out[i] = 0;
-    int dev = 0;
-    SATMI_HIP(hipGetDevice(&dev));
-    void *head = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_work_mu);
-        if ((int)g_work.size() > dev) {
-            auto it = g_work[dev].split.find((hipStream_t)stream);
-            auto last = g_work[dev].split_last.find((hipStream_t)stream);
-            if (it != g_work[dev].split.end() && last != g_work[dev].split_last.end() && last->second)
-                head = it->second.first;
-        }
-    }
-    if (!head) return SATMI_OK;   // the stream's last launch did not split: all zero (done = 0)
+    for (int i = 0; i < 7; ++i) out[i] = 0;   // a launch that did not split: all zero (done = 0)
     unsigned char h[SPLIT_HEAD_BYTES];
-    SATMI_HIP(hipStreamSynchronize((hipStream_t)stream));
-    SATMI_HIP(hipMemcpy(h, head, sizeof(h), hipMemcpyDeviceToHost));
-    dpll_split_decode(h, out);
+    bool split = false;
+    SATMI_TRY(split_head((hipStream_t)stream, h, &split));
+    if (split) dpll_split_decode(h, out);
     return SATMI_OK;
 }
 
@@ -1187,23 +1103,10 @@ extern "C" int satmi_dpll_split_busy(void *stream, int64_t *busy_ticks) {
         return SATMI_ERR_ARG;
     }
     *busy_ticks = 0;
-    int dev = 0;
-    SATMI_HIP(hipGetDevice(&dev));
-    void *head = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_work_mu);
-        if ((int)g_work.size() > dev) {
-            auto it = g_work[dev].split.find((hipStream_t)stream);
-            auto last = g_work[dev].split_last.find((hipStream_t)stream);
-            if (it != g_work[dev].split.end() && last != g_work[dev].split_last.end() && last->second)
-                head = it->second.first;
-        }
-    }
-    if (!head) return SATMI_OK;   // the stream's last launch did not split
     unsigned char h[SPLIT_HEAD_BYTES];
-    SATMI_HIP(hipStreamSynchronize((hipStream_t)stream));
-    SATMI_HIP(hipMemcpy(h, head, sizeof(h), hipMemcpyDeviceToHost));
-    *busy_ticks = dpll_split_busy(h);
+    bool split = false;
+    SATMI_TRY(split_head((hipStream_t)stream, h, &split));
+    if (split) *busy_ticks = dpll_split_busy(h);
     return SATMI_OK;
 }
 
@@ -1271,12 +1174,7 @@ extern "C" int satmi_dpll_plan(int max_vars, int max_clauses, int max_lits, int 
     }
     *kernel = SATMI_KERNEL_GENERAL;
     *lds_bytes_per_wave = lay.bytes;
-    int best = 0;
-    for (int wpg : {4, 2, 1}) {
-        const int wgs = std::min(16, (int)((160u * 1024u) / (lay.bytes * (uint32_t)wpg)));
-        if (wgs >= 1) best = std::max(best, std::min(32, wgs * wpg));
-    }
-    *waves_per_cu = best;
+    *waves_per_cu = narrow_shape(lay.bytes).waves_per_cu;
     return SATMI_OK;
 }
 
@@ -1337,15 +1235,22 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
                   "mode, no caller assignment, clause lengths 1..5, <= 2047 variables)");
         return SATMI_ERR_ARG;
     }
+    DpllLayout lay;
+    const bool wide = !scan_ok && (policy == SATMI_KERNEL_WIDE || !make_layout(max_vars, max_clauses, max_lits, &lay));
+    if (wide && !make_wide_layout(max_vars, max_clauses, max_lits, &lay)) {
+        set_error("satmi_dpll_batch_device: instance too large (wide layout: vars < 2^30, clauses <= 2^28, "
+                  "literals <= 2^30, < 4 GiB per wave)");
+        return SATMI_ERR_TOO_LARGE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    DpllStream *st = nullptr;
+    SATMI_TRY(dpll_stream(s, true, &st));
+    DeviceFacts dev;
+    SATMI_TRY(device_facts(&dev));
+    const uint64_t time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * dev.ticks_per_s) : 0;
+    st->split_last = false;   // until the launch takes splitting scratch, it has no split statistics
+    SATMI_HIP(hipMemsetAsync(st->counter, 0, 24, s));   // counter + launch span (common.h)
     if (scan_ok) {
-        DeviceWork *w = nullptr;
-        uint32_t *wc = nullptr;
-        int rc = device_work((hipStream_t)stream, &w, &wc);
-        if (rc) return rc;
-        int dev = 0, cus = 256;
-        SATMI_HIP(hipGetDevice(&dev));
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
         ScanLaunch Lc;
         Lc.num_instances = num_instances;
         Lc.inst_clause_begin = d_inst_clause_begin;
@@ -1358,7 +1263,7 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
         Lc.max_clause_len = max_clause_len;
         Lc.max_solutions = max_solutions;
         Lc.node_limit = node_limit;
-        Lc.time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * w->ticks_per_s) : 0;
+        Lc.time_limit_ticks = time_limit_ticks;
         Lc.sol_cap = sol_cap;
         Lc.sol_stride = sol_stride;
         Lc.status = d_status;
@@ -1367,11 +1272,9 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
         Lc.sol_lits = d_sol_lits;
         Lc.root_len = d_root_len;
         Lc.root_lits = d_root_lits;
-        Lc.work_counter = wc;
-        Lc.num_cus = cus;
-        Lc.stream = (hipStream_t)stream;
+        Lc.num_cus = dev.cus;
+        Lc.st = st;
         Lc.inc = inc;
-        Lc.occ_alloc = [stream](size_t bytes) { return occ_scratch((hipStream_t)stream, bytes); };
         // branch splitting reproduces the sequential search exactly only when
         // the search stops at its first model and nothing else cuts it short
         const int sm = g_split_enable.load();
@@ -1379,86 +1282,8 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
         Lc.split_always = sm == 2;
         Lc.split_helpers_per_cu = g_split_helpers.load();
         Lc.split_warmup = g_split_warmup.load();
-        Lc.split_alloc = [stream](size_t bytes, uint32_t *epoch) {
-            return split_scratch((hipStream_t)stream, bytes, epoch);
-        };
-        SATMI_HIP(hipMemsetAsync(wc, 0, 24, Lc.stream));   // counter + launch span (common.h)
-        split_mark_unsplit(Lc.stream);
         return dpll_scan_launch(Lc);
     }
-    DpllLayout lay;
-    const bool wide = policy == SATMI_KERNEL_WIDE || !make_layout(max_vars, max_clauses, max_lits, &lay);
-    if (wide && !make_wide_layout(max_vars, max_clauses, max_lits, &lay)) {
-        set_error("satmi_dpll_batch_device: instance too large (wide layout: vars < 2^30, clauses <= 2^28, "
-                  "literals <= 2^30, < 4 GiB per wave)");
-        return SATMI_ERR_TOO_LARGE;
-    }
-    DeviceWork *w = nullptr;
-    uint32_t *wc = nullptr;
-    int rc = device_work((hipStream_t)stream, &w, &wc);
-    if (rc) return rc;
-    split_mark_unsplit((hipStream_t)stream);   // this launch does not split: its stats are all zero
-    if (wide) {
-        // one-wave workgroups, each with an HBM arena; resident waves bounded by
-        // 32 per CU and by half the free device memory
-        int dev = 0, cus = 256;
-        SATMI_HIP(hipGetDevice(&dev));
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-        size_t free_b = 0, total_b = 0;
-        SATMI_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t per = lay.bytes;
-        const size_t by_mem = std::max<size_t>(1, (free_b / 2) / per);
-        const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)cus * 32, by_mem});
-        unsigned char *arena = (unsigned char *)arena_scratch((hipStream_t)stream, (size_t)grid * per);
-        if (!arena) return SATMI_ERR_NOMEM;
-        DpllArgs A;
-        A.inst_clause_begin = d_inst_clause_begin;
-        A.clause_lit_begin = d_clause_lit_begin;
-        A.lits = d_lits;
-        A.inst_nvars = d_inst_nvars;
-        A.init_begin = d_init_begin;
-        A.init_lits = d_init_lits;
-        A.num_instances = num_instances;
-        A.mode = mode;
-        A.sol_cap = sol_cap;
-        A.sol_stride = sol_stride;
-        A.max_solutions = max_solutions;
-        A.node_limit = node_limit;
-        A.time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * w->ticks_per_s) : 0;
-        A.status = d_status;
-        A.counters = d_counters;
-        A.sol_len = d_sol_len;
-        A.sol_lits = d_sol_lits;
-        A.root_len = d_root_len;
-        A.root_lits = d_root_lits;
-        A.work_counter = wc;
-        A.lay = lay;
-        hipStream_t s = (hipStream_t)stream;
-        SATMI_HIP(hipMemsetAsync(wc, 0, 24, s));   // counter + launch span (common.h)
-        hipLaunchKernelGGL(dpll_wide_kernel, dim3(grid), dim3(64), 0, s, A, arena);
-        SATMI_HIP(hipGetLastError());
-        return SATMI_OK;
-    }
-    // Occupancy is set by LDS: pick the workgroup shape that keeps the most
-    // waves resident (<= 32 waves and, conservatively, <= 16 workgroups per CU).
-    int waves_per_wg = 1, wg_per_cu = 1, best_waves = 0;
-    for (int wpg : {4, 2, 1}) {
-        const int wgs = std::min(16, (int)((160u * 1024u) / (lay.bytes * (uint32_t)wpg)));
-        const int waves = std::min(32, wgs * wpg);
-        if (wgs >= 1 && waves > best_waves) {
-            best_waves = waves;
-            waves_per_wg = wpg;
-            wg_per_cu = std::max(1, std::min(wgs, 32 / wpg));
-        }
-    }
-    const uint32_t wg_lds = lay.bytes * (uint32_t)waves_per_wg;
-    int dev = 0, cus = 256;
-    SATMI_HIP(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const int need = (num_instances + waves_per_wg - 1) / waves_per_wg;
-    const int grid = std::max(1, std::min(need, cus * wg_per_cu));
-
     DpllArgs A;
     A.inst_clause_begin = d_inst_clause_begin;
     A.clause_lit_begin = d_clause_lit_begin;
@@ -1472,22 +1297,40 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
     A.sol_stride = sol_stride;
     A.max_solutions = max_solutions;
     A.node_limit = node_limit;
-    A.time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * w->ticks_per_s) : 0;
+    A.time_limit_ticks = time_limit_ticks;
     A.status = d_status;
     A.counters = d_counters;
     A.sol_len = d_sol_len;
     A.sol_lits = d_sol_lits;
     A.root_len = d_root_len;
     A.root_lits = d_root_lits;
-    A.work_counter = wc;
+    A.work_counter = st->counter;
     A.lay = lay;
-
-    hipStream_t s = (hipStream_t)stream;
-    SATMI_HIP(hipMemsetAsync(wc, 0, 24, s));   // counter + launch span (common.h)
+    if (wide) {
+        // one-wave workgroups, each with an HBM arena; resident waves bounded by
+        // 32 per CU and by half the free device memory
+        size_t free_b = 0, total_b = 0;
+        SATMI_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t per = lay.bytes;
+        const size_t by_mem = std::max<size_t>(1, (free_b / 2) / per);
+        const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)dev.cus * 32, by_mem});
+        if (st->scratch(st->arena, (size_t)grid * per) != SATMI_OK) {
+            set_error("wide DPLL arenas: hipMalloc failed");
+            return SATMI_ERR_NOMEM;
+        }
+        hipLaunchKernelGGL(dpll_wide_kernel, dim3(grid), dim3(64), 0, s, A, st->arena.as<unsigned char>());
+        SATMI_HIP(hipGetLastError());
+        return SATMI_OK;
+    }
+    // Occupancy is set by LDS (narrow_shape: the shape satmi_dpll_plan reports)
+    const NarrowShape shape = narrow_shape(lay.bytes);
+    const uint32_t wg_lds = lay.bytes * (uint32_t)shape.waves_per_wg;
+    const int need = (num_instances + shape.waves_per_wg - 1) / shape.waves_per_wg;
+    const int grid = std::max(1, std::min(need, dev.cus * shape.wg_per_cu));
     if (wg_lds > 64u * 1024u)
         SATMI_HIP(hipFuncSetAttribute((const void *)dpll_batch_kernel,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds));
-    hipLaunchKernelGGL(dpll_batch_kernel, dim3(grid), dim3(64 * waves_per_wg), wg_lds, s, A);
+    hipLaunchKernelGGL(dpll_batch_kernel, dim3(grid), dim3(64 * shape.waves_per_wg), wg_lds, s, A);
     SATMI_HIP(hipGetLastError());
     return SATMI_OK;
 }

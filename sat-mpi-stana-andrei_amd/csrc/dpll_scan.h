@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <functional>
+#include "host.h"
 
 namespace satmi {
 
@@ -23,22 +23,16 @@ struct ScanLaunch {
     int32_t *status;
     int64_t *counters;
     int32_t *sol_len, *sol_lits, *root_len, *root_lits;
-    uint32_t *work_counter;
     int num_cus;
-    hipStream_t stream;
+    // the launch's stream with its work counter and scratch: the occurrence
+    // lists of the incremental kernel and the splitting scratch come from it
+    DpllStream *st;
     bool inc = false;   // incremental propagation (occurrence lists) instead of full clause scans
-    // incremental kernel: returns >= bytes of device scratch for the occurrence lists,
-    // valid for this launch on `stream` (nullptr on failure)
-    std::function<uint16_t *(size_t)> occ_alloc;
-    // branch splitting of the launch's tail (dpll_scan.hip, "Splitting the tail"):
-    // split_alloc returns >= bytes of device scratch valid for this launch on
-    // `stream` and the launch's tag for the slot states (distinct per launch on
-    // the stream), nullptr on failure
+    // branch splitting of the launch's tail (dpll_scan.hip, "Splitting the tail")
     bool split = false;
     bool split_always = false;   // split any eligible launch (else only 1 <= instances per resident wave <= 8)
     int split_helpers_per_cu = SPLIT_HELPERS_PER_CU;   // waves per CU that stay as helpers once the queue drains
     int split_warmup = SPLIT_WARMUP_NODES;   // nodes of a search before its first donation
-    std::function<void *(size_t, uint32_t *)> split_alloc;
 };
 
 // Can the scan kernel take a batch of this shape (SOUND mode, no caller
@@ -64,8 +58,8 @@ constexpr int SPLIT_HEAD_BYTES = 512;
 void dpll_split_decode(const void *head, int64_t out[7]);
 int64_t dpll_split_busy(const void *head);   // wave ticks the launch's waves spent searching
 
-// Launch on L.stream (asynchronous).  The caller has checked eligibility and
-// zeroed *L.work_counter on the stream.
+// Launch on L.st->stream (asynchronous).  The caller has checked eligibility and
+// zeroed L.st->counter on the stream.
 int dpll_scan_launch(const ScanLaunch &L);
 
 }  // namespace satmi

@@ -1977,18 +1977,37 @@ bool make_layout(int K, int max_vars, int max_clauses, bool with_lv, bool inc, u
     return o <= 160u * 1024u;
 }
 
-template <bool INC>
-const void *scan_fn(int K, int lvs) {   // occupancy queries: the split form (the larger register budget)
-    if (K == 3) {
-        if (lvs == 256) return (const void *)dpll_scan_kernel<3, 256, INC, true>;
-        if (lvs == 512) return (const void *)dpll_scan_kernel<3, 512, INC, true>;
-        if (lvs == 1024) return (const void *)dpll_scan_kernel<3, 1024, INC, true>;
-        return (const void *)dpll_scan_kernel<3, 0, INC, true>;
-    }
-    if (lvs == 512) return (const void *)dpll_scan_kernel<5, 512, INC, true>;
-    return lvs ? (const void *)dpll_scan_kernel<5, 4096, INC, true> : (const void *)dpll_scan_kernel<5, 0, INC, true>;
+// The kernel forms: one row per (K, static literal-state class; 0 = lv in the
+// dynamic image), instantiated for each (INC, SPLIT).  Occupancy queries and
+// launches both take their function from here.
+struct ScanForm {
+    int K, lvs;
+    const void *fn;
+};
+static_assert(2 * (Pack<3>::MAXV + 1) == 1024 && 2 * (Pack<5>::MAXV + 1) == 4096, "lv_static_class has a row each");
+template <bool INC, bool SPLIT>
+const void *scan_form(int K, int lvs) {
+    static const ScanForm forms[] = {{3, 256, (const void *)dpll_scan_kernel<3, 256, INC, SPLIT>},
+                                     {3, 512, (const void *)dpll_scan_kernel<3, 512, INC, SPLIT>},
+                                     {3, 1024, (const void *)dpll_scan_kernel<3, 1024, INC, SPLIT>},
+                                     {3, 0, (const void *)dpll_scan_kernel<3, 0, INC, SPLIT>},
+                                     {5, 512, (const void *)dpll_scan_kernel<5, 512, INC, SPLIT>},
+                                     {5, 4096, (const void *)dpll_scan_kernel<5, 4096, INC, SPLIT>},
+                                     {5, 0, (const void *)dpll_scan_kernel<5, 0, INC, SPLIT>}};
+    for (const ScanForm &f : forms)
+        if (f.K == K && f.lvs == lvs) return f.fn;
+    return nullptr;
 }
-const void *scan_fn(int K, int lvs, bool inc) { return inc ? scan_fn<true>(K, lvs) : scan_fn<false>(K, lvs); }
+// `fixed`: dpll_fixed_kernel<FIX_MCAP>, whatever K and lvs.  (The kernels are
+// emitted in the order they are first named in, and the compiler's output for
+// a few of them depends on that order: split forms, the fixed kernels, then
+// the unsplit forms keeps every kernel's machine code what it was.)
+const void *scan_fn(bool fixed, int K, int lvs, bool inc, bool split) {
+    if (split && !fixed) return inc ? scan_form<true, true>(K, lvs) : scan_form<false, true>(K, lvs);
+    if (fixed)
+        return split ? (const void *)dpll_fixed_kernel<FIX_MCAP, true> : (const void *)dpll_fixed_kernel<FIX_MCAP, false>;
+    return inc ? scan_form<true, false>(K, lvs) : scan_form<false, false>(K, lvs);
+}
 
 struct ScanPlan {
     int waves_per_wg = 1, wg_per_cu = 1, lvs = 0;
@@ -2006,7 +2025,7 @@ bool fixed_class(int K, int max_vars, int max_clauses, bool inc) {
 // cheaper gather addressing) whenever they reach the same residency.
 int scan_plan(int K, int max_vars, int max_clauses, bool inc, ScanPlan *P) {
     if (fixed_class(K, max_vars, max_clauses, inc)) {
-        const void *fn = (const void *)dpll_fixed_kernel<FIX_MCAP, true>;
+        const void *fn = scan_fn(true, K, 0, inc, true);
         int occ = 0, wgs = 32;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, 64, 0) == hipSuccess && occ > 0)
             wgs = std::min(wgs, occ);
@@ -2026,7 +2045,8 @@ int scan_plan(int K, int max_vars, int max_clauses, bool inc, ScanPlan *P) {
         const int lvs = wpg == 1 ? lv_static_class(K, max_vars) : 0;
         ScanLayout lay;
         if (!make_layout(K, max_vars, max_clauses, lvs == 0, inc, lvs == 256 ? 1u : 2u, &lay)) continue;
-        const void *fn = scan_fn(K, lvs, inc);
+        const void *fn = scan_fn(false, K, lvs, inc, true);   // the split form: the larger register budget
+        if (!fn) continue;
         const uint32_t wg_lds = lay.bytes * (uint32_t)wpg;
         const uint32_t wg_all = wg_lds + (uint32_t)lvs;
         if (wg_all > 160u * 1024u) continue;
@@ -2052,24 +2072,6 @@ int scan_plan(int K, int max_vars, int max_clauses, bool inc, ScanPlan *P) {
     return SATMI_OK;
 }
 
-template <bool INC, bool SPLIT>
-void launch_kernel(int K, int lvs, dim3 g, dim3 blk, uint32_t wg_lds, hipStream_t s, const ScanArgs &A) {
-    if (K == 3 && lvs == 256)
-        hipLaunchKernelGGL((dpll_scan_kernel<3, 256, INC, SPLIT>), g, blk, wg_lds, s, A);
-    else if (K == 3 && lvs == 512)
-        hipLaunchKernelGGL((dpll_scan_kernel<3, 512, INC, SPLIT>), g, blk, wg_lds, s, A);
-    else if (K == 3 && lvs == 1024)
-        hipLaunchKernelGGL((dpll_scan_kernel<3, 1024, INC, SPLIT>), g, blk, wg_lds, s, A);
-    else if (K == 3)
-        hipLaunchKernelGGL((dpll_scan_kernel<3, 0, INC, SPLIT>), g, blk, wg_lds, s, A);
-    else if (lvs == 512)
-        hipLaunchKernelGGL((dpll_scan_kernel<5, 512, INC, SPLIT>), g, blk, wg_lds, s, A);
-    else if (lvs)
-        hipLaunchKernelGGL((dpll_scan_kernel<5, 4096, INC, SPLIT>), g, blk, wg_lds, s, A);
-    else
-        hipLaunchKernelGGL((dpll_scan_kernel<5, 0, INC, SPLIT>), g, blk, wg_lds, s, A);
-}
-
 }  // namespace
 
 int64_t dpll_split_busy(const void *head) { return (int64_t)((const SplitCfg *)head)->busy; }
@@ -2086,14 +2088,19 @@ void dpll_split_decode(const void *head, int64_t out[7]) {
     out[6] = c->done;
 }
 
+// K of an eligible shape, 0 of any other
+static int eligible_k(int max_vars, int max_clauses, int max_lits, int max_clause_len, bool inc, uint32_t *lds_bytes) {
+    const int K = pick_k(max_vars, max_clause_len);
+    if (!K || max_lits > 65535) return 0;
+    ScanLayout lay;
+    if (!make_layout(K, max_vars, max_clauses, true, inc, 2u, &lay)) return 0;
+    if (lds_bytes) *lds_bytes = lay.bytes;
+    return K;
+}
+
 bool dpll_scan_eligible(int max_vars, int max_clauses, int max_lits, int max_clause_len, bool inc,
                         uint32_t *lds_bytes) {
-    const int K = pick_k(max_vars, max_clause_len);
-    if (!K || max_lits > 65535) return false;
-    ScanLayout lay;
-    if (!make_layout(K, max_vars, max_clauses, true, inc, 2u, &lay)) return false;
-    if (lds_bytes) *lds_bytes = lay.bytes;
-    return true;
+    return eligible_k(max_vars, max_clauses, max_lits, max_clause_len, inc, lds_bytes) != 0;
 }
 
 int dpll_scan_resident(int max_vars, int max_clauses, int max_clause_len, bool inc, int *waves_per_cu,
@@ -2123,12 +2130,13 @@ int dpll_scan_shape(int max_vars, int max_clauses, int max_clause_len, bool inc,
 }
 
 int dpll_scan_launch(const ScanLaunch &L) {
-    const int K = pick_k(L.max_vars, L.max_clause_len);
+    const int K = eligible_k(L.max_vars, L.max_clauses, L.max_lits, L.max_clause_len, L.inc, nullptr);
     ScanPlan P;
-    if (!K || !dpll_scan_eligible(L.max_vars, L.max_clauses, L.max_lits, L.max_clause_len, L.inc, nullptr)) {
+    if (!K) {
         set_error("dpll_scan_launch: batch shape not eligible for the scan kernel");
         return SATMI_ERR_ARG;
     }
+    hipStream_t stream = L.st->stream;
     const int prc = scan_plan(K, L.max_vars, L.max_clauses, L.inc, &P);
     if (prc) return prc;
     const ScanLayout &lay = P.lay;
@@ -2154,7 +2162,7 @@ int dpll_scan_launch(const ScanLaunch &L) {
     A.sol_lits = L.sol_lits;
     A.root_len = L.root_len;
     A.root_lits = L.root_lits;
-    A.work_counter = L.work_counter;
+    A.work_counter = L.st->counter;
     A.occ = nullptr;
     A.occ_cap = 0;
     A.occ_lists = 0;
@@ -2173,7 +2181,7 @@ int dpll_scan_launch(const ScanLaunch &L) {
     const int64_t waves = (int64_t)grid * waves_per_wg;
     const bool few = L.split_always || ((int64_t)L.num_instances <= (int64_t)SPLIT_MAX_PER_WAVE * waves &&
                                         (int64_t)L.num_instances >= (int64_t)L.num_cus * P.wg_per_cu * waves_per_wg);
-    if (L.split && L.split_alloc && few) {
+    if (L.split && few) {
         // slot pool: trail codes of the launch's entry width; one donation-stack
         // entry per decision frame per resident wave
         SplitCfg cfg{};
@@ -2201,11 +2209,11 @@ int dpll_scan_launch(const ScanLaunch &L) {
         const size_t pool = (size_t)cfg.slot_cap * (size_t)cfg.slot_bytes;
         const size_t stacks = (size_t)grid * (size_t)waves_per_wg * (size_t)cfg.dstack_cap * sizeof(int32_t);
         uint32_t epoch = 0;
-        void *p = L.split_alloc(SPLIT_POOL_OFF + pool + stacks, &epoch);
-        if (!p) {
+        if (L.st->split_scratch(SPLIT_POOL_OFF + pool + stacks, &epoch) != SATMI_OK) {
             set_error("dpll_scan_launch: no scratch for branch splitting");
             return SATMI_ERR_NOMEM;
         }
+        void *p = L.st->split.p;
         cfg.epoch = epoch & 0x0FFFFFFFu;
         // written by a one-wave kernel on the launch's stream, the header by
         // value in its arguments: a copy from this pageable host struct would
@@ -2213,7 +2221,7 @@ int dpll_scan_launch(const ScanLaunch &L) {
         // the stream's earlier work before it can queue the next launch -- the
         // two-stream overlap of the bench's steps was lost that way (split
         // form at full size: launch +1 %, step rate -5 %)
-        hipLaunchKernelGGL(split_init_kernel, dim3(1), dim3(64), 0, L.stream, (SplitCfg *)p, cfg);
+        hipLaunchKernelGGL(split_init_kernel, dim3(1), dim3(64), 0, stream, (SplitCfg *)p, cfg);
         A.split = (SplitCfg *)p;
     }
     // per resident wave: occurrence lists (max_lits entries, rounded to 128 B),
@@ -2223,21 +2231,20 @@ int dpll_scan_launch(const ScanLaunch &L) {
     A.occ_cap = A.occ_lists + snap_ovf;
     if (A.occ_cap > 0) {
         const size_t bytes = (size_t)grid * (size_t)waves_per_wg * (size_t)A.occ_cap * sizeof(uint16_t);
-        A.occ = L.occ_alloc ? L.occ_alloc(bytes) : nullptr;
-        if (!A.occ) {
+        if (L.st->scratch(L.st->occ, bytes) != SATMI_OK) {
             set_error("dpll_scan_launch: no per-wave scratch (occurrence lists / snapshot)");
             return SATMI_ERR_NOMEM;
         }
+        A.occ = L.st->occ.as<uint16_t>();
     }
-    const dim3 g(grid), blk(64 * waves_per_wg);
-    const bool sp = A.split != nullptr;
-    if (P.fixed && sp) hipLaunchKernelGGL((dpll_fixed_kernel<FIX_MCAP, true>), g, blk, 0, L.stream, A);
-    else if (P.fixed) hipLaunchKernelGGL((dpll_fixed_kernel<FIX_MCAP, false>), g, blk, 0, L.stream, A);
-    else if (L.inc && sp) launch_kernel<true, true>(K, P.lvs, g, blk, wg_lds, L.stream, A);
-    else if (L.inc) launch_kernel<true, false>(K, P.lvs, g, blk, wg_lds, L.stream, A);
-    else if (sp) launch_kernel<false, true>(K, P.lvs, g, blk, wg_lds, L.stream, A);
-    else launch_kernel<false, false>(K, P.lvs, g, blk, wg_lds, L.stream, A);
-    SATMI_HIP(hipGetLastError());
+    const void *fn = scan_fn(P.fixed, K, P.lvs, L.inc, A.split != nullptr);
+    if (!fn) {
+        set_error("dpll_scan_launch: no kernel form for the planned shape");
+        return SATMI_ERR_ARG;
+    }
+    void *params[] = {&A};
+    SATMI_HIP(hipLaunchKernel(fn, dim3(grid), dim3(64 * waves_per_wg), params, wg_lds, stream));
+    SATMI_HIP(hipGetLastError());   // the split_init_kernel launch too
     return SATMI_OK;
 }
 

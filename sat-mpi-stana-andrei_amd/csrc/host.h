@@ -1,0 +1,256 @@
+// host.h -- the host-side layer the solver translation units share (dpll.hip,
+// dpll_scan.hip, dp.hip, resolution.hip, cdcl.hip): the error-propagating
+// SATMI_TRY, the cached device facts, the grow-only device buffer, the
+// workspace pool with its lease, the dense variable index, and the DPLL
+// launches' per-stream state.  Host code only; device helpers are in common.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "common.h"
+
+namespace satmi {
+
+#define SATMI_TRY(x)                     \
+    do {                                 \
+        int _rc = (x);                   \
+        if (_rc != SATMI_OK) return _rc; \
+    } while (0)
+
+// ---------------------------------------------------------------- device facts
+// What the launch paths ask about the current device, queried once per device.
+struct DeviceFacts {
+    int cus = 256;               // compute units
+    double ticks_per_s = 1e8;    // s_memrealtime ticks per second (the constant wall clock)
+};
+inline int device_facts(DeviceFacts *out, int *dev_out = nullptr) {
+    static std::mutex mu;
+    static std::vector<std::pair<bool, DeviceFacts>> known;
+    int dev = 0;
+    SATMI_HIP(hipGetDevice(&dev));
+    if (dev_out) *dev_out = dev;
+    std::lock_guard<std::mutex> lk(mu);
+    if ((int)known.size() <= dev) known.resize(dev + 1);
+    auto &k = known[dev];
+    if (!k.first) {
+        int cus = 0, khz = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+            k.second.cus = cus;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess && khz > 0)
+            k.second.ticks_per_s = (double)khz * 1000.0;
+        k.first = true;
+    }
+    *out = k.second;
+    return SATMI_OK;
+}
+
+// ---------------------------------------------------------------- device buffer
+// Who ran out of device memory and what the caller can do about it.
+struct OomText {
+    const char *entry, *remedy;
+};
+
+// Grow-only device memory.  Three ways to get room, for three lifetimes:
+//   reserve  frees first and allocates exactly what is asked (contents lost):
+//            the lowest peak, for gigabyte candidate buffers and arenas;
+//   move_to  allocates exactly `want`, fills it, keeps a prefix by a copy on
+//            `s`, and frees the old buffer once `s` has drained;
+//   grow     move_to with half as much again, for buffers that grow step by step.
+// With `oom`, a request beyond the free device memory is SATMI_ERR_NOMEM with
+// that text; without, it is whatever hipMalloc answers.
+struct DevBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    int reserve(size_t bytes, const OomText *oom = nullptr) {
+        if (bytes <= cap) return SATMI_OK;
+        release();
+        const size_t want = std::max<size_t>(bytes, 256);
+        SATMI_TRY(alloc(&p, want, oom));
+        cap = want;
+        return SATMI_OK;
+    }
+    int move_to(size_t want, hipStream_t s, const OomText *oom, size_t keep = 0, int fill = -1) {
+        void *np = nullptr;
+        SATMI_TRY(alloc(&np, want, oom));
+        if (fill >= 0) SATMI_HIP(hipMemsetAsync(np, fill, want, s));
+        if (p && keep) SATMI_HIP(hipMemcpyAsync(np, p, std::min(keep, cap), hipMemcpyDeviceToDevice, s));
+        if (p) {
+            SATMI_HIP(hipStreamSynchronize(s));   // the old buffer is no longer read
+            (void)hipFree(p);
+        }
+        p = np;
+        cap = want;
+        return SATMI_OK;
+    }
+    int grow(size_t bytes, hipStream_t s, const OomText *oom, size_t keep = 0, int fill = -1) {
+        return bytes <= cap ? SATMI_OK : move_to(std::max<size_t>(bytes + bytes / 2, 256), s, oom, keep, fill);
+    }
+    template <class T>
+    T *as() const { return (T *)p; }
+
+private:
+    static int alloc(void **np, size_t want, const OomText *oom) {
+        size_t free_b = 0, total_b = 0;
+        if (oom && hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b) {
+            set_error(std::string(oom->entry) + ": out of device memory (" + std::to_string(want >> 20) +
+                      " MiB wanted, " + std::to_string(free_b >> 20) + " MiB free); " + oom->remedy);
+            return SATMI_ERR_NOMEM;
+        }
+        SATMI_HIP(hipMalloc(np, want));
+        return SATMI_OK;
+    }
+};
+
+// ---------------------------------------------------------------- workspace pool
+// The device state of one call of a solver (a workspace W: its buffers, a
+// non-blocking stream, pinned words), kept between calls in a process-wide
+// pool: a call takes a free workspace of its device or makes one, and returns
+// it when done, so concurrent calls from any number of host threads each own
+// one and the number of workspaces is the peak number of concurrent calls.
+// W has `int dev`, `hipStream_t stream` and `bool open()` (creates the stream
+// and whatever else a fresh workspace needs).
+template <class W>
+struct Pool {
+    static Pool &get() {
+        static Pool *p = new Pool;   // never destroyed: no hipFree after the runtime's teardown
+        return *p;
+    }
+    W *acquire(int dev) {
+        {
+            std::lock_guard<std::mutex> g(mu);
+            for (size_t i = 0; i < free_list.size(); ++i)
+                if (free_list[i]->dev == dev) {
+                    W *w = free_list[i];
+                    free_list.erase(free_list.begin() + (long)i);
+                    return w;
+                }
+        }
+        W *w = new W;
+        w->dev = dev;
+        if (!w->open()) {
+            delete w;
+            return nullptr;
+        }
+        return w;
+    }
+    void release(W *w) {
+        std::lock_guard<std::mutex> g(mu);
+        free_list.push_back(w);
+    }
+    // Free every idle workspace; calls in flight keep theirs.
+    void trim() {
+        std::vector<W *> idle;
+        {
+            std::lock_guard<std::mutex> g(mu);
+            idle.swap(free_list);
+        }
+        for (W *w : idle) destroy(w);
+    }
+    static void destroy(W *w) {
+        (void)hipStreamSynchronize(w->stream);
+        delete w;
+    }
+
+private:
+    std::mutex mu;
+    std::vector<W *> free_list;
+};
+
+// A call's hold on a workspace: back to the pool after a call that set `ok`,
+// destroyed (once its stream drained) after one that failed part-way and may
+// have left device state that the next call would trust.
+template <class W>
+struct Lease {
+    W *w;
+    bool ok = false;
+    ~Lease() {
+        if (!w) return;
+        if (ok) Pool<W>::get().release(w);
+        else Pool<W>::destroy(w);
+    }
+};
+
+// ---------------------------------------------------------------- dense variable index
+// Checks the literals of a formula (0 and INT32_MIN are errors, reported under
+// the caller's name `who`) and numbers the variables that occur, in ascending
+// order of their ids: var2dense[v] = index or -1, dense2var[index] = v.
+inline int dense_var_index(const char *who, const int32_t *lits, int64_t nlits, int *maxvar,
+                           std::vector<int32_t> *var2dense, std::vector<int32_t> *dense2var) {
+    int mv = 0;
+    for (int64_t i = 0; i < nlits; ++i) {
+        if (lits[i] == 0 || lits[i] == INT32_MIN) {
+            set_error(std::string(who) + ": literal 0 / INT32_MIN");
+            return SATMI_ERR_ARG;
+        }
+        mv = std::max(mv, std::abs(lits[i]));
+    }
+    var2dense->assign((size_t)mv + 1, -1);
+    dense2var->clear();
+    for (int64_t i = 0; i < nlits; ++i) (*var2dense)[std::abs(lits[i])] = 1;
+    for (int v = 1; v <= mv; ++v)
+        if ((*var2dense)[v] >= 0) {
+            (*var2dense)[v] = (int32_t)dense2var->size();
+            dense2var->push_back(v);
+        }
+    *maxvar = mv;
+    return SATMI_OK;
+}
+
+// ---------------------------------------------------------------- DPLL stream state
+// What the DPLL launches keep per (device, stream); dpll.hip owns the map and
+// looks a stream's state up once per launch.  Each stream has its own work
+// counter, so batches launched on different streams (a pipelined caller
+// overlapping one batch's tail with the next batch) never share a queue.
+// Launches on one stream are ordered, and its state belongs to whoever is
+// launching on it: a scratch buffer is only replaced after the stream drained.
+struct DpllStream {
+    hipStream_t stream = nullptr;
+    uint32_t *counter = nullptr;   // work counter + launch span (common.h), 256 B
+    DevBuf occ;                    // incremental scan kernel: occurrence lists / snapshot overflow per wave
+    DevBuf split;                  // branch splitting: head, slot pool, donation stacks
+    DevBuf arena;                  // wide general kernel: per-wave HBM arenas
+    uint32_t split_epoch = 0;      // the launch tag of the slot states
+    bool split_last = false;       // the stream's last DPLL launch split (its statistics are valid)
+
+    int scratch(DevBuf &b, size_t bytes) {
+        if (bytes <= b.cap) return SATMI_OK;
+        if (b.p) SATMI_HIP(hipStreamSynchronize(stream));
+        return b.reserve(bytes);
+    }
+    // >= bytes of splitting scratch and the next launch tag (distinct per
+    // launch on the stream); marks the launch as one that split
+    int split_scratch(size_t bytes, uint32_t *epoch) {
+        if (bytes > split.cap) {
+            SATMI_TRY(scratch(split, bytes));
+            // fresh memory: no stale state may carry the next tags
+            const hipError_t e = hipMemsetAsync(split.p, 0, split.cap, stream);
+            if (e != hipSuccess) {
+                split.release();
+                return hip_fail(e, "branch-splitting scratch: hipMemsetAsync");
+            }
+        }
+        split_epoch = (split_epoch + 1u) & 0x0FFFFFFFu;
+        if (split_epoch == 0u) split_epoch = 1u;
+        *epoch = split_epoch;
+        split_last = true;
+        return SATMI_OK;
+    }
+};
+
+}  // namespace satmi

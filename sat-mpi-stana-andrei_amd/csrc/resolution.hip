@@ -35,11 +35,11 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "common.h"
+#include "host.h"
 #include "prims.h"
 
 namespace satmi {
@@ -702,34 +702,9 @@ __global__ void __launch_bounds__(256) res_gather_kernel(ResArgs A) {
 // ------------------------------------------------------------------ host side
 namespace {
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-    // grow to `bytes` (contents not kept); SATMI_ERR_NOMEM with a hint when the
-    // device cannot hold it
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SATMI_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(bytes, (size_t)256);
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && want > free_b) {
-            set_error("satmi_resolution_host: out of device memory (" + std::to_string(want >> 20) + " MiB wanted, " +
-                      std::to_string(free_b >> 20) + " MiB free); bound the saturation with clause_limit / "
-                      "max_passes");
-            return SATMI_ERR_NOMEM;
-        }
-        SATMI_HIP(hipMalloc(&p, want));
-        cap = want;
-        return SATMI_OK;
-    }
-    template <class T>
-    T *as() const { return (T *)p; }
-};
+// The buffers are sized by the pass at hand and can reach gigabytes: they are
+// freed before they are regrown, to exactly what is asked (DevBuf::reserve).
+constexpr OomText RES_OOM{"satmi_resolution_host", "bound the saturation with clause_limit / max_passes"};
 
 // Pinned host memory, grow-only: the call's inputs are gathered here and sent
 // in one copy (a copy from pageable memory is staged synchronously, one per
@@ -751,12 +726,6 @@ struct PinBuf {
         return SATMI_OK;
     }
 };
-
-#define SATMI_TRY(x)                  \
-    do {                              \
-        int _rc = (x);                \
-        if (_rc != SATMI_OK) return _rc; \
-    } while (0)
 
 uint64_t table_slots(int64_t keys) {
     uint64_t cap = 1024;
@@ -815,13 +784,12 @@ struct EventTimer {
     }
 };
 
-// Device buffers of satmi_resolution_host, kept between calls (grow-only) in a
-// process-wide pool: a call takes a free workspace of its device (or makes
-// one) and returns it when done, so concurrent calls from any number of host
-// threads each own one, overlap on the device (each its own non-blocking
-// stream), and the number of workspaces is the peak number of concurrent
-// calls.  A saturation of a small formula is a few passes of small launches,
-// so allocating its buffers per call cost more than its kernels.
+// Device buffers of satmi_resolution_host, kept between calls (grow-only) in
+// the workspace pool (host.h): concurrent calls overlap on the device, each on
+// its own non-blocking stream.  A saturation of a small formula is a few
+// passes of small launches, so allocating its buffers per call cost more than
+// its kernels.  A call that failed part-way destroys its workspace: its table
+// may hold stale keys.
 // The packed path's first segment of a call (state init, key packing, table
 // seeding, the first batch of passes, the state's copy back), captured into a
 // HIP graph the second time the same segment is enqueued and replayed from
@@ -868,51 +836,9 @@ struct ResWork {
         if (stream) (void)hipStreamDestroy(stream);
         if (pin) (void)hipHostFree(pin);
     }
-};
-
-struct ResPool {
-    std::mutex mu;
-    std::vector<ResWork *> free_list;
-};
-ResPool &res_pool() {
-    static ResPool *p = new ResPool;   // never destroyed: no hipFree after the runtime's teardown
-    return *p;
-}
-ResWork *res_acquire(int dev) {
-    ResPool &P = res_pool();
-    {
-        std::lock_guard<std::mutex> g(P.mu);
-        for (size_t i = 0; i < P.free_list.size(); ++i)
-            if (P.free_list[i]->dev == dev) {
-                ResWork *w = P.free_list[i];
-                P.free_list.erase(P.free_list.begin() + (long)i);
-                return w;
-            }
-    }
-    ResWork *w = new ResWork;
-    w->dev = dev;
-    if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipHostMalloc((void **)&w->pin, 64, hipHostMallocCoherent) != hipSuccess) {
-        delete w;
-        return nullptr;
-    }
-    return w;
-}
-// A call's hold on a workspace: back to the pool after a call that completed,
-// destroyed after one that failed part-way (its table may hold stale keys).
-struct ResLease {
-    ResWork *w;
-    bool ok = false;
-    ~ResLease() {
-        if (!w) return;
-        if (ok) {
-            ResPool &P = res_pool();
-            std::lock_guard<std::mutex> g(P.mu);
-            P.free_list.push_back(w);
-        } else {
-            (void)hipStreamSynchronize(w->stream);
-            delete w;
-        }
+    bool open() {
+        return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
+               hipHostMalloc((void **)&pin, 64, hipHostMallocCoherent) == hipSuccess;
     }
 };
 
@@ -955,13 +881,7 @@ void record_pass(const std::vector<uint64_t> &hkeys, int64_t nnew, bool packed, 
 // grow the packed key buffer to >= want keys, keeping keys [0, keep)
 int grow_keys(ResWork &wk, int64_t want, int64_t keep, hipStream_t s) {
     if ((size_t)want * 8 <= wk.keys.cap) return SATMI_OK;
-    DevBuf grown;
-    SATMI_TRY(grown.reserve(8 * (size_t)want));
-    if (keep > 0) SATMI_HIP(hipMemcpyAsync(grown.p, wk.keys.p, 8 * (size_t)keep, hipMemcpyDeviceToDevice, s));
-    std::swap(grown.p, wk.keys.p);
-    std::swap(grown.cap, wk.keys.cap);
-    SATMI_HIP(hipStreamSynchronize(s));   // before `grown` frees the old buffer
-    return SATMI_OK;
+    return wk.keys.move_to(8 * (size_t)want, s, &RES_OOM, 8 * (size_t)std::max<int64_t>(keep, 0));
 }
 
 // The packed path (<= 31 variables): the clause keys, the table and the state
@@ -983,13 +903,13 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
     const int PCAP = std::max(1, std::min(pass_cap, 1 << 16));   // passes whose counts the device keeps
     // the state and the per-pass counts in one buffer (one copy back per batch)
     const size_t SOFF = (sizeof(ResState) + 255) & ~(size_t)255;
-    SATMI_TRY(wk.keys.reserve(8 * (size_t)std::max<int64_t>(4 * (int64_t)nclauses, 1 << 14)));
-    SATMI_TRY(wk.state.reserve(SOFF + 8 * (size_t)PCAP));
-    SATMI_TRY(wk.stripes.reserve(8 * RES_STRIPE_ALLOC));
+    SATMI_TRY(wk.keys.reserve(8 * (size_t)std::max<int64_t>(4 * (int64_t)nclauses, 1 << 14), &RES_OOM));
+    SATMI_TRY(wk.state.reserve(SOFF + 8 * (size_t)PCAP, &RES_OOM));
+    SATMI_TRY(wk.stripes.reserve(8 * RES_STRIPE_ALLOC, &RES_OOM));
     SATMI_TRY(wk.pstate.reserve(SOFF + 8 * (size_t)PCAP, hipHostMallocCoherent));
     int64_t key_cap = (int64_t)(wk.keys.cap / 8);
     // stripe regions: twice the key room (the stripes fill unevenly)
-    SATMI_TRY(wk.stage.reserve(8 * 2 * (size_t)key_cap));
+    SATMI_TRY(wk.stage.reserve(8 * 2 * (size_t)key_cap, &RES_OOM));
     // the table: a power of two >= 2x the keys it can hold (load <= 1/2; a
     // table larger than needed only spreads the probes over more cache lines)
     const auto slots_for = [](int64_t nkeys) {   // a power of two, >= 8 buckets
@@ -998,7 +918,7 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
         return c;
     };
     uint64_t tslots = slots_for(key_cap);
-    SATMI_TRY(wk.table.reserve(8 * tslots));
+    SATMI_TRY(wk.table.reserve(8 * tslots, &RES_OOM));
     // the clean slate of the next call (the whole table emptied); cond: only
     // if the batch just copied out ended the saturation
     const auto reset = [&](int cond) -> int {
@@ -1033,8 +953,9 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
                        wk.keys.as<uint64_t>(), wk.table.as<uint64_t>(), tslots / RES_BUCKET - 1,
                        wk.state.as<ResState>());
     SATMI_HIP(hipGetLastError());
-    double hz = 1e8;
-    (void)satmi_wallclock_hz(&hz);
+    DeviceFacts dev;
+    SATMI_TRY(device_facts(&dev));
+    const double hz = dev.ticks_per_s;
     ResArgs A;
     std::memset(&A, 0, sizeof(A));   // padding too: the first segment's graph is keyed by these bytes
     const auto args = [&]() {
@@ -1154,9 +1075,9 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
             // stripe regions: twice the key room, and 5/4 of the fullest stripe
             // of the stopped pass (the finish kernel reset the stripes)
             const int64_t region = std::max<int64_t>(2 * key_cap / RES_STRIPES, st.stripe_max + st.stripe_max / 4 + 1024);
-            SATMI_TRY(wk.stage.reserve(8 * (size_t)RES_STRIPES * (size_t)region));
+            SATMI_TRY(wk.stage.reserve(8 * (size_t)RES_STRIPES * (size_t)region, &RES_OOM));
             tslots = slots_for(key_cap);
-            SATMI_TRY(wk.table.reserve(8 * tslots));
+            SATMI_TRY(wk.table.reserve(8 * tslots, &RES_OOM));
             args();
             st.overflow = 0;
             st.spill = 0;
@@ -1257,20 +1178,8 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     // dense variable index (variables sorted by id)
     const int64_t L = nclauses > 0 ? h_clause_off[nclauses] : 0;
     int maxvar = 0;
-    for (int64_t i = 0; i < L; ++i) {
-        if (h_lits[i] == 0 || h_lits[i] == INT32_MIN) {
-            set_error("satmi_resolution_host: literal 0 / INT32_MIN");
-            return SATMI_ERR_ARG;
-        }
-        maxvar = std::max(maxvar, std::abs(h_lits[i]));
-    }
-    std::vector<int32_t> var2dense(maxvar + 1, -1), dense2var;
-    for (int64_t i = 0; i < L; ++i) var2dense[std::abs(h_lits[i])] = 1;
-    for (int v = 1; v <= maxvar; ++v)
-        if (var2dense[v] >= 0) {
-            var2dense[v] = (int32_t)dense2var.size();
-            dense2var.push_back(v);
-        }
+    std::vector<int32_t> var2dense, dense2var;
+    SATMI_TRY(dense_var_index("satmi_resolution_host", h_lits, L, &maxvar, &var2dense, &dense2var));
     const int V = (int)dense2var.size();
     const int W = std::max(1, (V + 63) / 64);
     const int K = 2 * W;
@@ -1278,7 +1187,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     const int64_t slot_base = g_slot_base;
     int dev_id = 0;
     SATMI_HIP(hipGetDevice(&dev_id));
-    ResLease lease{res_acquire(dev_id)};
+    Lease<ResWork> lease{Pool<ResWork>::get().acquire(dev_id)};
     if (!lease.w) {
         set_error("satmi_resolution_host: hipStreamCreate failed");
         return SATMI_ERR_HIP;
@@ -1291,11 +1200,11 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const size_t o_lits = al(4 * (size_t)(nclauses + 1)), o_map = o_lits + al(4 * (size_t)std::max<int64_t>(L, 1));
     const size_t up_bytes = o_map + al(4 * (size_t)(maxvar + 1));
-    SATMI_TRY(wk->up.reserve(up_bytes));
+    SATMI_TRY(wk->up.reserve(up_bytes, &RES_OOM));
     SATMI_TRY(wk->up_h.reserve(up_bytes));
     int64_t ncl = nclauses;
-    SATMI_TRY(clauses.reserve(8 * (size_t)std::max<int64_t>(ncl, 1) * K));
-    SATMI_TRY(counters.reserve(64));
+    SATMI_TRY(clauses.reserve(8 * (size_t)std::max<int64_t>(ncl, 1) * K, &RES_OOM));
+    SATMI_TRY(counters.reserve(64, &RES_OOM));
     if (nclauses > 0) {
         // (the previous call's copy out of up_h finished: every call ends with a wait)
         std::memcpy(wk->up_h.p, h_clause_off, 4 * (size_t)(nclauses + 1));
@@ -1334,7 +1243,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     // a fresh table holding clauses [0, nkeys) with room for `room` keys
     const auto rebuild_table = [&](int64_t nkeys, int64_t room) {
         tcap = table_slots(room);
-        SATMI_TRY(table.reserve(8 * tcap));
+        SATMI_TRY(table.reserve(8 * tcap, &RES_OOM));
         SATMI_HIP(hipMemsetAsync(table.p, 0xFF, 8 * tcap, s));   // HT_EMPTY
         if (nkeys > 0 && packed)
             hipLaunchKernelGGL(ht_clauses_packed_kernel, dim3(grid_for(nkeys)), dim3(PRIM_BLOCK), 0, s,
@@ -1371,13 +1280,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     };
     const auto grow_clauses = [&](int64_t want) {
         if ((size_t)want * K * 8 <= clauses.cap) return SATMI_OK;
-        DevBuf grown;
-        SATMI_TRY(grown.reserve(8 * (size_t)want * K * 2));
-        SATMI_HIP(hipMemcpyAsync(grown.p, clauses.p, clauses.cap, hipMemcpyDeviceToDevice, s));
-        std::swap(grown.p, clauses.p);
-        std::swap(grown.cap, clauses.cap);
-        SATMI_HIP(hipStreamSynchronize(s));   // before `grown` frees the old array
-        return SATMI_OK;
+        return clauses.move_to(8 * (size_t)want * K * 2, s, &RES_OOM, clauses.cap);   // twice the room, every clause kept
     };
 
     int64_t jlo = 0, rec_clauses = 0, rec_lits = 0;
@@ -1403,7 +1306,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             j1 = std::min(ncl, std::max(j1, j0 + 1));
             while (j1 > j0 + 1 && (j1 * (j1 - 1) - j0 * (j0 - 1)) / 2 > PAIR_CHUNK) --j1;
             const int64_t npairs = std::max<int64_t>(1, (j1 * (j1 - 1) - j0 * (j0 - 1)) / 2);
-            SATMI_TRY(cand.reserve(std::min(8 * (size_t)npairs * K, std::max(g_cand_bytes, cand.cap))));
+            SATMI_TRY(cand.reserve(std::min(8 * (size_t)npairs * K, std::max(g_cand_bytes, cand.cap)), &RES_OOM));
             struct {
                 unsigned long long count;
                 int empty;
@@ -1427,7 +1330,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
                     set_error("satmi_resolution_host: candidate buffer overflow after a re-run");
                     return SATMI_ERR_HIP;
                 }
-                SATMI_TRY(cand.reserve(8 * (size_t)counted * K));   // overflowed: re-run at the counted size
+                SATMI_TRY(cand.reserve(8 * (size_t)counted * K, &RES_OOM));   // overflowed: re-run at the counted size
             }
             g_stats.pairs += npairs;
             j0 = j1;
@@ -1438,11 +1341,11 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             const int64_t nc = (int64_t)(hc.count - (unsigned long long)slot_base);
             if (nc <= 0) continue;
             if ((uint64_t)(ncl + nnew + nc) > tcap / 2) SATMI_TRY(rebuild_table(ncl + nnew, 2 * (ncl + nnew + nc)));
-            SATMI_TRY(flag.reserve(8 * (size_t)nc));
-            SATMI_TRY(pos.reserve(8 * (size_t)nc));
-            SATMI_TRY(slotv.reserve(8 * (size_t)nc));
-            SATMI_TRY(tiles.reserve(8 * (size_t)((nc + SCAN_TILE - 1) / SCAN_TILE + 1)));
-            SATMI_TRY(grand.reserve(8));
+            SATMI_TRY(flag.reserve(8 * (size_t)nc, &RES_OOM));
+            SATMI_TRY(pos.reserve(8 * (size_t)nc, &RES_OOM));
+            SATMI_TRY(slotv.reserve(8 * (size_t)nc, &RES_OOM));
+            SATMI_TRY(tiles.reserve(8 * (size_t)((nc + SCAN_TILE - 1) / SCAN_TILE + 1), &RES_OOM));
+            SATMI_TRY(grand.reserve(8, &RES_OOM));
             t_claims.begin(s);
             if (packed)
                 hipLaunchKernelGGL(ht_cand_packed_kernel, dim3(grid_for(nc)), dim3(PRIM_BLOCK), 0, s,
@@ -1502,15 +1405,6 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
 // Free every idle workspace of this solver (device buffers, streams, pinned
 // words); calls in flight keep theirs.  The next call allocates afresh.
 extern "C" int satmi_resolution_trim(void) {
-    std::vector<ResWork *> idle;
-    {
-        auto &P = res_pool();
-        std::lock_guard<std::mutex> g(P.mu);
-        idle.swap(P.free_list);
-    }
-    for (ResWork *w : idle) {
-        (void)hipStreamSynchronize(w->stream);
-        delete w;
-    }
+    Pool<ResWork>::get().trim();
     return SATMI_OK;
 }
