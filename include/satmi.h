@@ -191,6 +191,13 @@ int satmi_launch_chain_floor(int launches, int reps, double *us_per_launch);
 int satmi_dp_last_stats(int64_t *steps, int64_t *subset_tests, int64_t *new_clauses, int64_t *launches,
                         int *words, double *device_ms);
 
+/* How often the calling thread's last satmi_dp_host call grew a buffer and ran
+ * a step again, per buffer that ran out: out[0] the pair-sized scratch, out[1]
+ * the clause-list arrays, out[2] the image arena, out[3] the assembly scratch
+ * (a step that ran out of several counts once in each).  All zero for a call
+ * whose workspace was already large enough. */
+int satmi_dp_last_resumes(int32_t out[4]);
+
 /* Free the idle device workspaces that satmi_dp_host / satmi_resolution_host
  * keep between calls (buffers only grow while kept); calls in flight keep theirs. */
 int satmi_dp_trim(void);

@@ -850,10 +850,11 @@ __global__ void __launch_bounds__(POP_THREADS) dp_pop_split_kernel(DpArgs A) {
         int ex = cp | (cq << 16);
         er = cr;
         block_excl_scan2(ex, er, wsum, tot, tr);
+        // (unsigned: a neg half of 2^15 or more sets the word's sign bit)
         ep = ex & 0xFFFF;
-        en = ex >> 16;
+        en = (int)((uint32_t)ex >> 16);
         np = tot & 0xFFFF;
-        nn = tot >> 16;
+        nn = (uint32_t)tot >> 16;
     } else {
         int tn;
         ep = block_excl_scan(cp, wsum, tot);
@@ -925,7 +926,8 @@ __global__ void __launch_bounds__(POP_THREADS) dp_pop_split_kernel(DpArgs A) {
     const int capA = (int)cap_for(mxA), capB = (int)cap_for(mxB), capR = (int)cap_for((int64_t)mxA + mxB);
     if (tid == 0) {
         const bool fit = it < A.inline_steps && npairs <= INL_PMAX && lds_fp && K <= INL_KMAX &&
-                         nr + npairs <= A.ncl_cap && S->arena_top + npairs * 2 * capR <= A.arena_cap;
+                         nr + npairs <= A.ncl_cap && S->arena_top + npairs * 2 * capR <= A.arena_cap &&
+                         npairs * 2 * ((int64_t)capA + capB) <= A.xs_cap;   // (dp_assemble_kernel's scratch, skip = 2)
         sh_quit = fit ? 0 : 1;
     }
     wg_sync();
@@ -1527,7 +1529,7 @@ __global__ void __launch_bounds__(64 * ASM_WAVES) dp_assemble_kernel(DpArgs A) {
                 O.fill[t] = L.fill[c];
                 O.used[t] = L.used[c];
             }
-            if (lane < K) O.bits[t * K + lane] = L.bits[c * K + lane];
+            for (int w = lane; w < K; w += 64) O.bits[t * K + w] = L.bits[c * K + w];   // (K > 64 past 2,048 variables)
             first_positions(A.arena + L.off[c], mask);
         } else {
             const int64_t k = t - nr;
@@ -1581,7 +1583,7 @@ __global__ void __launch_bounds__(64 * ASM_WAVES) dp_assemble_kernel(DpArgs A) {
                 O.fill[t] = (int32_t)rf;
                 O.used[t] = (int32_t)ru;
             }
-            if (lane < K) O.bits[t * K + lane] = A.rbits[(uint64_t)p * K + lane];
+            for (int w = lane; w < K; w += 64) O.bits[t * K + w] = A.rbits[(uint64_t)p * K + w];
         }
         wave_sync();   // the wave's scratch is rewritten by its next clause
     }
@@ -1615,6 +1617,7 @@ struct DpStats {
     int64_t steps = 0, tests = 0, new_clauses = 0, launches = 0;
     double device_ms = 0.0;
     int words = 0;
+    int32_t resumes[4] = {0, 0, 0, 0};   // steps run again, per overflow bit (OVF_PAIRS .. OVF_XS)
 };
 thread_local DpStats g_dp_stats;   // the calling thread's last call
 
@@ -1968,6 +1971,7 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
         }
         if (st.overflow) {   // grow what ran out, then run the step again
             const int cur = st.cur;
+            for (int b = 0; b < 4; ++b) g_dp_stats.resumes[b] += (st.overflow >> b) & 1;
             if (st.overflow & OVF_PAIRS) SATMI_TRY(grow_pairs(Wk, st.need[0], K));
             if (st.overflow & OVF_NCL) SATMI_TRY(grow_ncl(Wk, st.need[1], K, cur, st.ncl));
             if (st.overflow & OVF_ARENA) {
@@ -2058,6 +2062,15 @@ extern "C" int satmi_dp_last_stats(int64_t *steps, int64_t *subset_tests, int64_
     if (launches) *launches = g_dp_stats.launches;
     if (words) *words = g_dp_stats.words;
     if (device_ms) *device_ms = g_dp_stats.device_ms;
+    return SATMI_OK;
+}
+
+extern "C" int satmi_dp_last_resumes(int32_t out[4]) {
+    if (!out) {
+        set_error("satmi_dp_last_resumes: bad arguments");
+        return SATMI_ERR_ARG;
+    }
+    for (int b = 0; b < 4; ++b) out[b] = g_dp_stats.resumes[b];
     return SATMI_OK;
 }
 

@@ -30,7 +30,7 @@ EXPORTED = (
     "satmi_dp_host", "satmi_dpll_scan_lds_bytes", "satmi_dpll_set_kernel", "satmi_dpll_plan",
     "satmi_dpll_launch_span", "satmi_wallclock_hz", "satmi_resolution_debug_slot_base",
     "satmi_resolution_last_stats", "satmi_resolution_last_clock", "satmi_dpll_set_split", "satmi_dpll_split_stats",
-    "satmi_dp_last_stats",
+    "satmi_dp_last_stats", "satmi_dp_last_resumes",
     "satmi_cdcl_batch_host", "satmi_dpll_set_split_warmup", "satmi_resolution_debug_cand_bytes",
     "satmi_dp_trim", "satmi_resolution_trim", "satmi_cdcl_last_stats", "satmi_launch_chain_floor",
     "satmi_dpll_split_busy", "satmi_dpll_scan_shape",
@@ -139,6 +139,7 @@ def load():
     L.satmi_resolution_debug_cand_bytes.argtypes = [ctypes.c_int64]
     L.satmi_cdcl_last_stats.argtypes = [P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_int)]
     L.satmi_dp_last_stats.argtypes = [i64p, i64p, i64p, i64p, P(ctypes.c_int), P(ctypes.c_double)]
+    L.satmi_dp_last_resumes.argtypes = [i32p]
     L.satmi_cdcl_batch_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, ctypes.c_int64, ctypes.c_int64,
                                         ctypes.c_double, i32p, i32p, i32p, ctypes.c_int, i64p,
                                         P(ctypes.c_double)]

@@ -53,15 +53,19 @@ def eliminate(formula, step_limit=0, clause_limit=0, time_limit=0.0, record=Fals
 
 def last_stats():
     """Work of the last eliminate() call in this thread (satmi_dp_last_stats):
-    steps, subset tests, new resolvents, kernel launches, key words and the
-    device time of the elimination steps (ms)."""
+    steps, subset tests, new resolvents, kernel launches, key words, the
+    device time of the elimination steps (ms), and how often a step was run
+    again after each buffer ran out (satmi_dp_last_resumes)."""
     v = [ctypes.c_int64(0) for _ in range(4)]
     w = ctypes.c_int(0)
     ms = ctypes.c_double(0.0)
     _capi.check(_capi.load().satmi_dp_last_stats(*(ctypes.byref(x) for x in v), ctypes.byref(w), ctypes.byref(ms)),
                 "satmi_dp_last_stats")
+    rs = (ctypes.c_int32 * 4)()
+    _capi.check(_capi.load().satmi_dp_last_resumes(rs), "satmi_dp_last_resumes")
     return {"steps": v[0].value, "subset_tests": v[1].value, "new_clauses": v[2].value,
-            "launches": v[3].value, "words": w.value, "device_ms": ms.value}
+            "launches": v[3].value, "words": w.value, "device_ms": ms.value,
+            "resumes": dict(zip(("pairs", "clauses", "arena", "scratch"), rs))}
 
 
 def davis_putnam_solve(formula, time_limit=0.0):
