@@ -125,7 +125,14 @@ int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
  *   *passes   completed passes that added clauses; pass_new[p] = clauses added
  *   optional record (all three non-NULL): clauses new in pass p are
  *   rec_pass_off[p] .. rec_pass_off[p+1] in rec_clause_off / rec_lits, each
- *   clause as ascending literals.
+ *   clause as ascending literals, the clauses of a pass in ascending order.
+ *   The record arrays are truncated at their capacities, silently: a pass's
+ *   record stops before the first clause that does not fit rec_lit_cap
+ *   literals or rec_clause_cap offsets (it is then a prefix of the pass's
+ *   sorted clauses, later passes add what still fits), and passes from
+ *   rec_pass_cap - 1 on are not recorded.  Nothing is written past an array's
+ *   capacity.  *result, *passes and pass_new are not truncated by the record:
+ *   pass_new[p] is exact for every p < pass_cap whatever was recorded.
  */
 int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, const int32_t *h_lits,
                           int64_t max_passes, int64_t clause_limit, double time_limit_s,
@@ -144,6 +151,22 @@ int satmi_resolution_last_stats(int64_t *pairs, int64_t *candidates, double *pai
  * pass, so an issue roofline prices the pipes at the clock the kernel ran
  * at.  0 when no pass kernel ran (the general path beyond 31 variables). */
 int satmi_resolution_last_clock(double *shader_hz);
+
+/* What the calling thread's last satmi_resolution_host call regrew or ran
+ * again; fills out[0 .. min(n, SATMI_RES_REGROWTHS)).  At most 31 variables
+ * (the fused pass; the other words stay 0): passes run again because
+ *   out[0]  a stage stripe held only a part of the pass's new keys,
+ *   out[1]  the clause list outgrew the key buffer (no stripe spilled),
+ *   out[2]  the table stopped the pass (neither of the above).
+ * Beyond 31 variables (out[0 .. 3) stay 0):
+ *   out[3]  pair chunks run (one per pass unless a pass has more than 2^27 pairs),
+ *   out[4]  chunks run again at the counted size of their candidates,
+ *   out[5]  tables rebuilt in the middle of a pass,
+ *   out[6]  growths of the clause buffer.
+ * out[0 .. 3) and out[4], out[6] are zero for a call whose workspace was
+ * already large enough. */
+#define SATMI_RES_REGROWTHS 7
+int satmi_resolution_last_regrowths(int64_t *out, int n);
 
 /* Test knob: the first append slot (default 0) of the pair kernel's candidates
  * (more than 31 variables) or of a pass's new clauses (at most 31), so a small

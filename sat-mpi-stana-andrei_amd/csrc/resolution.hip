@@ -753,6 +753,17 @@ struct ResStats {
 };
 thread_local ResStats g_stats;   // the calling thread's last call
 
+// What the calling thread's last call regrew (satmi_resolution_last_regrowths).
+// Packed path: passes run again because the stage spilled, because the clause
+// list outgrew the key buffer (no spill), or because the table stopped the
+// pass.  General path: pair chunks run, chunks run again at the counted
+// candidate size, tables rebuilt in the middle of a pass, clause-buffer growths.
+struct ResRegrow {
+    int64_t stage = 0, keys = 0, table = 0;
+    int64_t chunks = 0, cand_reruns = 0, table_rebuilds = 0, clause_growths = 0;
+};
+thread_local ResRegrow g_regrow;
+
 // Times launches on one stream: begin() / end() bracket them, total() sums.
 struct EventTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -976,6 +987,7 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
     };
     args();
     g_stats = ResStats{};
+    g_regrow = ResRegrow{};
     const bool record = h_rec_lits && h_rec_clause_off && h_rec_pass_off;
     int64_t rec_clauses = 0, rec_lits = 0;
     std::vector<uint64_t> hkeys;
@@ -1064,6 +1076,12 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
             if (time_limit_s > 0 &&
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count() >= time_limit_s)
                 break;   // past the deadline: a timeout after the completed passes (result -1)
+            if (st.spill)
+                ++g_regrow.stage;
+            else if (st.ncl + (int64_t)st.count > key_cap)
+                ++g_regrow.keys;
+            else
+                ++g_regrow.table;
             // twice the claims of the stopped pass (all of its new keys when
             // the pass ran to its end -- the key buffer or the stage ran out,
             // the stage's excess counted, not stored; a part of them when the
@@ -1136,6 +1154,18 @@ extern "C" int satmi_resolution_last_clock(double *shader_hz) {
         return SATMI_ERR_ARG;
     }
     *shader_hz = g_stats.shader_hz;
+    return SATMI_OK;
+}
+
+extern "C" int satmi_resolution_last_regrowths(int64_t *out, int n) {
+    if (!out || n < 0) {
+        set_error("satmi_resolution_last_regrowths: bad arguments");
+        return SATMI_ERR_ARG;
+    }
+    const int64_t v[SATMI_RES_REGROWTHS] = {g_regrow.stage,  g_regrow.keys,        g_regrow.table,
+                                            g_regrow.chunks, g_regrow.cand_reruns, g_regrow.table_rebuilds,
+                                            g_regrow.clause_growths};
+    for (int k = 0; k < n && k < SATMI_RES_REGROWTHS; ++k) out[k] = v[k];
     return SATMI_OK;
 }
 
@@ -1237,6 +1267,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     t_pairs.reset();
     t_claims.reset();
     g_stats = ResStats{};
+    g_regrow = ResRegrow{};
     uint64_t tcap = 0;
     unsigned long long *d_count = counters.as<unsigned long long>();
     int *d_empty = (int *)(counters.as<char>() + 8);
@@ -1280,6 +1311,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     };
     const auto grow_clauses = [&](int64_t want) {
         if ((size_t)want * K * 8 <= clauses.cap) return SATMI_OK;
+        ++g_regrow.clause_growths;
         return clauses.move_to(8 * (size_t)want * K * 2, s, &RES_OOM, clauses.cap);   // twice the room, every clause kept
     };
 
@@ -1330,9 +1362,11 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
                     set_error("satmi_resolution_host: candidate buffer overflow after a re-run");
                     return SATMI_ERR_HIP;
                 }
+                ++g_regrow.cand_reruns;
                 SATMI_TRY(cand.reserve(8 * (size_t)counted * K, &RES_OOM));   // overflowed: re-run at the counted size
             }
             g_stats.pairs += npairs;
+            ++g_regrow.chunks;
             j0 = j1;
             if (hc.empty) {   // an empty resolvent: unsatisfiable (REF.py:84-85)
                 empty = true;
@@ -1340,7 +1374,10 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             }
             const int64_t nc = (int64_t)(hc.count - (unsigned long long)slot_base);
             if (nc <= 0) continue;
-            if ((uint64_t)(ncl + nnew + nc) > tcap / 2) SATMI_TRY(rebuild_table(ncl + nnew, 2 * (ncl + nnew + nc)));
+            if ((uint64_t)(ncl + nnew + nc) > tcap / 2) {
+                ++g_regrow.table_rebuilds;
+                SATMI_TRY(rebuild_table(ncl + nnew, 2 * (ncl + nnew + nc)));
+            }
             SATMI_TRY(flag.reserve(8 * (size_t)nc, &RES_OOM));
             SATMI_TRY(pos.reserve(8 * (size_t)nc, &RES_OOM));
             SATMI_TRY(slotv.reserve(8 * (size_t)nc, &RES_OOM));

@@ -20,6 +20,8 @@ COUNTER_NAMES = ("nodes", "decisions", "unit_props", "pure_assigns", "conflicts"
 DPLL_EXHAUSTED, DPLL_STOPPED, DPLL_NODE_LIMIT, DPLL_TIMEOUT, DPLL_TOO_LARGE = range(5)
 STATUS_NAMES = {0: "exhausted", 1: "stopped", 2: "node_limit", 3: "timeout", 4: "too_large"}
 RES_SAT, RES_UNSAT, RES_LIMIT = 1, 0, -1
+# satmi_resolution_last_regrowths: the words of its out array, in order
+RES_REGROWTHS = ("stage", "keys", "table", "chunks", "cand_reruns", "table_rebuilds", "clause_growths")
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_SCAN, KERNEL_INC, KERNEL_WIDE = 0, 1, 2, 3, 4
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
@@ -33,7 +35,7 @@ EXPORTED = (
     "satmi_dp_last_stats", "satmi_dp_last_resumes",
     "satmi_cdcl_batch_host", "satmi_dpll_set_split_warmup", "satmi_resolution_debug_cand_bytes",
     "satmi_dp_trim", "satmi_resolution_trim", "satmi_cdcl_last_stats", "satmi_launch_chain_floor",
-    "satmi_dpll_split_busy", "satmi_dpll_scan_shape",
+    "satmi_dpll_split_busy", "satmi_dpll_scan_shape", "satmi_resolution_last_regrowths",
 )
 
 
@@ -146,6 +148,7 @@ def load():
     L.satmi_resolution_last_stats.argtypes = [i64p, i64p, ctypes.POINTER(ctypes.c_double),
                                               ctypes.POINTER(ctypes.c_double)]
     L.satmi_resolution_last_clock.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.satmi_resolution_last_regrowths.argtypes = [i64p, ctypes.c_int]
     L.satmi_launch_chain_floor.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
     L.satmi_dp_host.argtypes = [
         ctypes.c_int, i32p, i32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, i32p, i32p, ctypes.c_int, i32p,

@@ -69,7 +69,11 @@ def resolve(formula, max_passes=0, clause_limit=0, time_limit=0.0, record=False,
 def last_stats():
     """Work and device time of the last resolve() call: pairs, candidate
     resolvents, pair-kernel ms, claim (hash dedup) kernel ms, and the pass
-    kernels' live shader clock (Hz; 0 on the general path)."""
+    kernels' live shader clock (Hz; 0 on the general path); "regrowths": what
+    the call regrew or ran again (satmi_resolution_last_regrowths) -- passes of
+    the packed path run again for the stage / the key buffer / the table, and
+    the general path's chunks, candidate-buffer re-runs, mid-pass table
+    rebuilds and clause-buffer growths."""
     L = _capi.load()
     pairs, cand = ctypes.c_int64(0), ctypes.c_int64(0)
     pms, cms = ctypes.c_double(0.0), ctypes.c_double(0.0)
@@ -77,8 +81,10 @@ def last_stats():
                                               ctypes.byref(cms)), "satmi_resolution_last_stats")
     hz = ctypes.c_double(0.0)
     _capi.check(L.satmi_resolution_last_clock(ctypes.byref(hz)), "satmi_resolution_last_clock")
+    rg = (ctypes.c_int64 * len(_capi.RES_REGROWTHS))()
+    _capi.check(L.satmi_resolution_last_regrowths(rg, len(rg)), "satmi_resolution_last_regrowths")
     return {"pairs": pairs.value, "candidates": cand.value, "pair_ms": pms.value, "claim_ms": cms.value,
-            "shader_clock_hz": hz.value}
+            "shader_clock_hz": hz.value, "regrowths": dict(zip(_capi.RES_REGROWTHS, rg))}
 
 
 def resolution_solve(formula, time_limit=0.0):
