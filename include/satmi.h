@@ -179,6 +179,41 @@ int satmi_resolution_debug_slot_base(int64_t base);
 int satmi_resolution_debug_cand_bytes(int64_t bytes);
 
 /*
+ * Batched resolution saturation: many small clause sets in one launch, one
+ * workgroup per formula, each saturated entirely in LDS (CSR host arrays as
+ * satmi_dpll_batch_host / satmi_cdcl_batch_host).  A formula takes this path
+ * when it has at most 31 distinct variables and never holds more keys than the
+ * launch's capacity -- chosen from the batch: the smallest of 256 / 1,024 /
+ * 2,560 / 4,096 keys that holds 3^d + m for every formula of d <= 31 variables
+ * and m clauses, else 4,096; any other formula gets h_result[b] =
+ * SATMI_RES_BATCH_UNFIT and is left to satmi_resolution_host.  There is no
+ * time limit: a formula's work is bounded by its capacity.
+ *   max_passes / clause_limit   <= 0: unlimited (the rule of satmi_resolution_host:
+ *                 stop after the first pass that takes the clause count over clause_limit)
+ *   h_result[b], h_passes[b]    as satmi_resolution_host's *result / *passes
+ *   h_pass_new    [B x pass_cap] rows, zero-filled, exact for every pass < pass_cap
+ *   optional record (all three non-NULL): satmi_resolution_host's format and
+ *   truncation rules, formula after formula through rec_clause_off / rec_lits;
+ *   formula b's pass p is clauses rec_pass_off[b * (pass_cap + 1) + p] ..
+ *   rec_pass_off[b * (pass_cap + 1) + p + 1]
+ * For an UNFIT formula only h_result[b] carries information: h_passes[b] is 0
+ * and its pass_new row all zero.  Arguments are checked before any HIP call
+ * (num_instances == 0 returns SATMI_OK).  Thread-safe like satmi_resolution_host.
+ */
+#define SATMI_RES_BATCH_UNFIT (-2)
+int satmi_resolution_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                int64_t max_passes, int64_t clause_limit,
+                                int32_t *h_result, int32_t *h_passes, int64_t *h_pass_new, int pass_cap,
+                                int32_t *h_rec_lits, int64_t rec_lit_cap, int64_t *h_rec_clause_off,
+                                int64_t rec_clause_cap, int64_t *h_rec_pass_off /* [B x (pass_cap + 1)] */);
+
+/* Test knob of satmi_resolution_batch_host (0 = default): at most `grid`
+ * workgroups are launched, and a formula holds at most `key_cap` keys, so a few
+ * dozen tiny formulas exercise workgroup reuse and the UNFIT path. */
+int satmi_resolution_debug_batch(int grid, int key_cap);
+
+/*
  * Davis-Putnam elimination, replaces davis_putnam_solver (REF.py:98-130) for one
  * clause set.  Variables are eliminated in the reference's order (CPython's
  * `set.pop()` on the variable set, modelled on the device), resolvents are

@@ -20,6 +20,7 @@ COUNTER_NAMES = ("nodes", "decisions", "unit_props", "pure_assigns", "conflicts"
 DPLL_EXHAUSTED, DPLL_STOPPED, DPLL_NODE_LIMIT, DPLL_TIMEOUT, DPLL_TOO_LARGE = range(5)
 STATUS_NAMES = {0: "exhausted", 1: "stopped", 2: "node_limit", 3: "timeout", 4: "too_large"}
 RES_SAT, RES_UNSAT, RES_LIMIT = 1, 0, -1
+RES_BATCH_UNFIT = -2   # satmi_resolution_batch_host: the formula is left to satmi_resolution_host
 # satmi_resolution_last_regrowths: the words of its out array, in order
 RES_REGROWTHS = ("stage", "keys", "table", "chunks", "cand_reruns", "table_rebuilds", "clause_growths")
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_SCAN, KERNEL_INC, KERNEL_WIDE = 0, 1, 2, 3, 4
@@ -36,6 +37,7 @@ EXPORTED = (
     "satmi_cdcl_batch_host", "satmi_dpll_set_split_warmup", "satmi_resolution_debug_cand_bytes",
     "satmi_dp_trim", "satmi_resolution_trim", "satmi_cdcl_last_stats", "satmi_launch_chain_floor",
     "satmi_dpll_split_busy", "satmi_dpll_scan_shape", "satmi_resolution_last_regrowths",
+    "satmi_resolution_batch_host", "satmi_resolution_debug_batch",
 )
 
 
@@ -137,6 +139,10 @@ def load():
     L.satmi_resolution_host.argtypes = [
         ctypes.c_int, i32p, i32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
         i32p, i32p, i64p, ctypes.c_int, i32p, ctypes.c_int64, i64p, ctypes.c_int64, i64p, ctypes.c_int]
+    L.satmi_resolution_batch_host.argtypes = [
+        ctypes.c_int, i32p, i32p, i32p, ctypes.c_int64, ctypes.c_int64,
+        i32p, i32p, i64p, ctypes.c_int, i32p, ctypes.c_int64, i64p, ctypes.c_int64, i64p]
+    L.satmi_resolution_debug_batch.argtypes = [ctypes.c_int, ctypes.c_int]
     L.satmi_resolution_debug_slot_base.argtypes = [ctypes.c_int64]
     L.satmi_resolution_debug_cand_bytes.argtypes = [ctypes.c_int64]
     L.satmi_cdcl_last_stats.argtypes = [P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_int)]

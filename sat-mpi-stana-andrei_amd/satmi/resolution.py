@@ -66,6 +66,111 @@ def resolve(formula, max_passes=0, clause_limit=0, time_limit=0.0, record=False,
     return out
 
 
+# Per-pass counts a batched call keeps per formula at first (a saturation of a
+# small set rarely takes more than a dozen passes); a formula with more passes
+# is run again with room for every pass its capacity allows.
+_PASS_CAP = 32
+_PASS_CAP_MAX = 4096   # the largest key capacity: every completed pass adds a key
+
+
+def debug_batch(grid=0, key_cap=0):
+    """Test knob of resolve_batch (satmi_resolution_debug_batch; 0 = default): at most
+    `grid` workgroups, at most `key_cap` keys per formula."""
+    _capi.check(_capi.load().satmi_resolution_debug_batch(int(grid), int(key_cap)), "satmi_resolution_debug_batch")
+
+
+def _batch_call(L, cb, max_passes, clause_limit, record, pcap, rec_cap):
+    """One satmi_resolution_batch_host call -> (result[B], passes[B], pass_new[B, pcap], clauses or None),
+    clauses[b][p] = the sorted clauses formula b's pass p added."""
+    B = cb.num_instances
+    res = np.zeros(B, dtype=np.int32)
+    passes = np.zeros(B, dtype=np.int32)
+    pass_new = np.zeros((B, pcap), dtype=np.int64)
+    icb, clb, lits = (np.ascontiguousarray(a, dtype=np.int32)
+                      for a in (cb.inst_clause_begin, cb.clause_lit_begin, cb.lits))
+    args = (B, _p(icb), _p(clb), _p(lits), int(max_passes), int(clause_limit),
+            _p(res), _p(passes), _p(pass_new, ctypes.c_int64), pcap)
+    if not record:
+        _capi.check(L.satmi_resolution_batch_host(*args, None, 0, None, 0, None), "satmi_resolution_batch_host")
+        return res, passes, pass_new, None
+    while True:
+        rl = np.zeros(rec_cap, dtype=np.int32)
+        rco = np.zeros(rec_cap + 1, dtype=np.int64)
+        rpo = np.zeros((B, pcap + 1), dtype=np.int64)
+        _capi.check(L.satmi_resolution_batch_host(*args, _p(rl), rec_cap, _p(rco, ctypes.c_int64), rec_cap + 1,
+                                                  _p(rpo, ctypes.c_int64)), "satmi_resolution_batch_host")
+        # the record is truncated silently at its capacities: complete iff it holds every counted clause
+        if int(rpo[-1, -1]) == int(pass_new.sum()):
+            break
+        rec_cap *= 4
+    clauses = [[[rl[rco[c]:rco[c + 1]].tolist() for c in range(rpo[b, p], rpo[b, p + 1])]
+                for p in range(min(int(passes[b]), pcap))] for b in range(B)]
+    return res, passes, pass_new, clauses
+
+
+def resolve_batch(formulas, max_passes=0, clause_limit=0, time_limit=0.0, record=False, rec_cap=1 << 20):
+    """resolve() for many small formulas in one launch (csrc/resolution_batch.hip:
+    one workgroup per formula, saturated in LDS).  `formulas` is a list of
+    formulas or a cnf.CnfBatch; returns the list of resolve()'s dicts, each
+    with "path": "batch", or "single" for a formula the batched kernel does not
+    take (more than 31 variables, or more clauses than its capacity), which is
+    run through resolve() -- `time_limit` applies to those calls only: the
+    batched kernel's work is bounded by its capacity."""
+    from . import cnf
+    L = _capi.load()
+    if isinstance(formulas, cnf.CnfBatch):
+        cb = formulas
+    else:
+        formulas = list(formulas)
+        cb = cnf.pack(formulas) if formulas else None
+    if cb is None or cb.num_instances == 0:
+        return []
+    _capi.require_gpu()
+    B = cb.num_instances
+    pcap = int(max_passes) if 0 < max_passes < _PASS_CAP else _PASS_CAP
+    res, passes, pass_new, clauses = _batch_call(L, cb, max_passes, clause_limit, record, pcap, rec_cap)
+    out = []
+    for b in range(B):
+        if res[b] == _capi.RES_BATCH_UNFIT:
+            r = resolve(cb.instance(b), max_passes=max_passes, clause_limit=clause_limit, time_limit=time_limit,
+                        record=record)
+            r["path"] = "single"
+        else:
+            n = int(passes[b])
+            r = {"result": int(res[b]), "passes": n, "pass_new": pass_new[b, :min(n, pcap)].tolist()}
+            if record:
+                r["clauses"] = clauses[b]
+            r["path"] = "batch"
+        out.append(r)
+    # formulas with more passes than the first call kept counts for: once more, with room for all
+    more = [b for b in range(B) if out[b]["path"] == "batch" and out[b]["passes"] > pcap]
+    if more:
+        sub = cnf.pack([cb.instance(b) for b in more])
+        res, passes, pass_new, clauses = _batch_call(L, sub, max_passes, clause_limit, record, _PASS_CAP_MAX, rec_cap)
+        for k, b in enumerate(more):
+            if res[k] == _capi.RES_BATCH_UNFIT:   # (the same capacity rule: not expected)
+                out[b] = resolve(cb.instance(b), max_passes=max_passes, clause_limit=clause_limit,
+                                 time_limit=time_limit, record=record)
+                out[b]["path"] = "single"
+                continue
+            n = int(passes[k])
+            out[b] = {"result": int(res[k]), "passes": n, "pass_new": pass_new[k, :n].tolist()}
+            if record:
+                out[b]["clauses"] = clauses[k]
+            out[b]["path"] = "batch"
+    return out
+
+
+def resolution_solve_batch(formulas, time_limit=0.0):
+    """resolution_solve for a list of formulas (or a cnf.CnfBatch) -> List[bool]."""
+    out = []
+    for r in resolve_batch(formulas, time_limit=time_limit):
+        if r["result"] < 0:
+            raise ResolutionLimit(f"resolution stopped by its limit after {r['passes']} passes")
+        out.append(bool(r["result"]))
+    return out
+
+
 def last_stats():
     """Work and device time of the last resolve() call: pairs, candidate
     resolvents, pair-kernel ms, claim (hash dedup) kernel ms, and the pass

@@ -92,6 +92,13 @@ def resolution_solver(formula: Formula) -> bool:
     return resolution_solve(formula, time_limit=_time_limit)
 
 
+def resolution_solver_batch(formulas: List[Formula]) -> List[bool]:
+    """resolution_solver for many formulas in one launch (small formulas are
+    saturated one per workgroup; the others go through resolution_solver's path)."""
+    from .resolution import resolution_solve_batch
+    return resolution_solve_batch(formulas, time_limit=_time_limit)
+
+
 def davis_putnam_solver(formula: Formula) -> bool:
     from .dp import davis_putnam_solve
     return davis_putnam_solve(formula, time_limit=_time_limit)
