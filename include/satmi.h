@@ -77,11 +77,20 @@ int satmi_stream_synchronize(void *stream);
  *   node_limit     stop after this many dpll calls (0 = none)
  *   time_limit_s   per-instance wall-clock limit (<= 0 = none)
  *   max_vars/max_clauses/max_lits   maxima over the batch (size the LDS layout)
- *   max_clause_len longest clause of the batch, with every clause non-empty;
- *                  0 = unknown.  SOUND mode without a caller assignment and
- *                  1 <= max_clause_len <= 5, max_vars <= 2047 runs the
- *                  clause-scan kernel (same results; see satmi_dpll_set_kernel);
- *                  an instance that breaks the promise gets SATMI_DPLL_TOO_LARGE
+ *   max_clause_len longest clause of the batch; a value of 1..5 also promises
+ *                  that every clause is non-empty; 0 = unknown.  SOUND mode
+ *                  without a caller assignment and 1 <= max_clause_len <= 5,
+ *                  max_vars <= 2047 runs the clause-scan kernel (same results;
+ *                  see satmi_dpll_set_kernel); an instance that breaks the
+ *                  promise gets SATMI_DPLL_TOO_LARGE.  A value above 255 takes
+ *                  the general kernel's wide form (SATMI_KERNEL_WIDE), since
+ *                  the LDS form holds clauses of at most 255 literals.  A
+ *                  caller that passes 0 is planned by max_vars/max_clauses/
+ *                  max_lits alone: where those fit the LDS layout, an instance
+ *                  with a longer clause gets SATMI_DPLL_TOO_LARGE, as it does
+ *                  under a pinned SATMI_KERNEL_GENERAL.
+ *                  satmi_dpll_batch_host passes the true maximum whenever it
+ *                  is above 5 or no clause is empty, else 0.
  *   d_init_begin/d_init_lits        optional caller assignment (REF.py:133's
  *                  `assignment`), as signed literals in dict order; may be NULL
  *   sol_cap        solutions stored per instance; sol_stride >= max assignment size
@@ -319,13 +328,18 @@ uint64_t satmi_dpll_scan_lds_bytes(int max_vars, int max_clauses, int max_lits, 
  *   INC      the clause kernel with incremental rounds (only the clauses that lost
  *            a literal are read); an ineligible call fails with SATMI_ERR_ARG
  *   WIDE     the general kernel in its wide form (see SATMI_KERNEL_WIDE)
- * All give identical statuses, counters and models. */
+ * All give identical statuses, counters and models, but for one status: the
+ * LDS form of the general kernel holds clauses of at most 255 literals, so under
+ * a pinned GENERAL (or with max_clause_len = 0, unknown) an instance with a
+ * longer clause whose batch fits the LDS layout gets SATMI_DPLL_TOO_LARGE, where
+ * AUTO and WIDE solve it. */
 #define SATMI_KERNEL_AUTO 0
 #define SATMI_KERNEL_GENERAL 1
 #define SATMI_KERNEL_SCAN 2
 #define SATMI_KERNEL_INC 3
 #define SATMI_KERNEL_WIDE 4   /* the general kernel with its image in a per-wave HBM arena (32-bit
-                                 indices); AUTO takes it for batches beyond the LDS layout */
+                                 indices; clauses of at most 65,535 literals); AUTO takes it for batches
+                                 beyond the LDS layout or with a clause of more than 255 literals */
 int satmi_dpll_set_kernel(int policy);
 
 /* Branch splitting in the clause kernels (process-wide; default on): once a
@@ -368,7 +382,7 @@ int satmi_dpll_split_stats(void *stream, int64_t *out);
 int satmi_dpll_split_busy(void *stream, int64_t *busy_ticks);
 
 /* The launch satmi_dpll_batch_device would make for this batch shape under the
- * current policy: *kernel = SATMI_KERNEL_SCAN or SATMI_KERNEL_GENERAL, LDS
+ * current policy: *kernel = SATMI_KERNEL_SCAN, _INC, _GENERAL or _WIDE, LDS
  * bytes per wavefront, and wavefronts resident per CU (LDS and registers). */
 int satmi_dpll_plan(int max_vars, int max_clauses, int max_lits, int max_clause_len, int mode, int has_init,
                     int *kernel, uint64_t *lds_bytes_per_wave, int *waves_per_cu);

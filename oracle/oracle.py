@@ -27,20 +27,25 @@ def _rebuild():
     subprocess.run(["make", "-s", "-B", "-C", _HERE], check=True)
 
 
+# entry points a library kept from an older tree lacks
+_NEWEST_ENTRIES = ("oracle_cdcl_paths", "oracle_dpll_paths")
+
+
 def _open(path=_LIB, rebuild=_rebuild):
     """The library at `path`, rebuilt once if it predates an entry point this
     module binds (a library kept from an older tree): never a silent pass."""
     L = ctypes.CDLL(path)
-    if hasattr(L, "oracle_cdcl_paths"):
+    if all(hasattr(L, n) for n in _NEWEST_ENTRIES):
         return L
     import _ctypes
     _ctypes.dlclose(L._handle)   # or the next CDLL returns the old mapping
     del L
     rebuild()
     L = ctypes.CDLL(path)
-    if not hasattr(L, "oracle_cdcl_paths"):
+    missing = [n for n in _NEWEST_ENTRIES if not hasattr(L, n)]
+    if missing:
         _ctypes.dlclose(L._handle)
-        raise RuntimeError(f"{path} has no oracle_cdcl_paths after a rebuild: a stale oracle library")
+        raise RuntimeError(f"{path} has no {', '.join(missing)} after a rebuild: a stale oracle library")
     return L
 
 
@@ -56,6 +61,8 @@ def lib():
         L.oracle_dpll.argtypes = [ctypes.c_int, ctypes.c_int, i32p, i32p, ctypes.c_int, ctypes.c_int64,
                                   ctypes.c_int64, i32p, ctypes.c_int, i32p, ctypes.c_int64, i64p,
                                   ctypes.c_int64, i32p, P(ctypes.c_int), P(Counters)]
+        L.oracle_dpll_paths.restype = ctypes.c_int
+        L.oracle_dpll_paths.argtypes = L.oracle_dpll.argtypes + [i64p, ctypes.c_int]
         L.oracle_dp.restype = ctypes.c_int
         L.oracle_dp.argtypes = [ctypes.c_int, i32p, i32p, ctypes.c_int64, ctypes.c_int64, i32p, ctypes.c_int,
                                 P(ctypes.c_int), i32p, ctypes.c_int64, i64p, ctypes.c_int64, i64p, ctypes.c_int]
@@ -91,10 +98,26 @@ def _p(a, t=ctypes.c_int32):
     return a.ctypes.data_as(ctypes.POINTER(t))
 
 
-def dpll(formula, mode="ref", max_solutions=0, node_limit=0, init=None, sol_cap=1 << 16):
+# The path counters of oracle_dpll_paths, in the order of sat_oracle.c's DP_*
+# (which says what each counts): which code paths of csrc/dpll.hip a formula
+# drives.  Maxima of an index are -1 where the event never happened.
+DPLL_PATHS = (
+    "snapshot_len_max", "collected_snapshot_len_max", "stamp_drop_len_max", "mismatch_index_max",
+    "emptied_index_max", "undone_after_stop_max", "cut_round_len_max", "snapshot_same_var_same_sign",
+    "snapshot_same_var_opposite_sign", "snapshot_same_var_earlier_chunk", "skip_assigned_equal",
+    "empty_clause_with_units", "empty_clause_no_units", "empty_clause_first_index_max",
+    "occ_single_len_max", "flat_total_max", "flat_list_straddles_window", "unit_clause_index_max",
+    "conflict_clauses_max", "pure_count_max", "pure_first_pos_max", "branch_var_max",
+    "branch_tie_across_groups", "undo_len_max", "undo_non_effective", "init_overwrite",
+    "init_var_beyond_formula", "init_mismatch", "decision_mismatch", "sols_past_cap", "clause_len_max",
+    "model_mismatch")
+
+
+def dpll(formula, mode="ref", max_solutions=0, node_limit=0, init=None, sol_cap=1 << 16, paths=False):
     """Run the DPLL restatement.  mode 'ref' = REF.py:133-214 exactly; 'sound' =
     decisions applied as unit clauses.  Returns dict with status, solutions
-    (lists of signed literals in assignment-dict order), counters, root_assign."""
+    (lists of signed literals in assignment-dict order), counters, root_assign;
+    with paths=True also "paths": DPLL_PATHS of the same search."""
     off, lits = _csr(formula)
     nv = max([abs(l) for c in formula for l in c] + [abs(l) for l in (init or [])] + [1])
     init_a = np.array(list(init or []) or [0], dtype=np.int32)
@@ -104,15 +127,25 @@ def dpll(formula, mode="ref", max_solutions=0, node_limit=0, init=None, sol_cap=
     root = np.zeros(nv + 1, dtype=np.int32)
     root_len = ctypes.c_int(0)
     ctr = Counters()
-    st = lib().oracle_dpll(nv, len(formula), _p(off), _p(lits), 0 if mode == "ref" else 1,
-                           max_solutions, node_limit, _p(init_a), len(init or []),
-                           _p(sol_lits), cap_l, _p(sol_off, ctypes.c_int64), sol_cap,
-                           _p(root), ctypes.byref(root_len), ctypes.byref(ctr))
+    args = (nv, len(formula), _p(off), _p(lits), 0 if mode == "ref" else 1,
+            max_solutions, node_limit, _p(init_a), len(init or []),
+            _p(sol_lits), cap_l, _p(sol_off, ctypes.c_int64), sol_cap,
+            _p(root), ctypes.byref(root_len), ctypes.byref(ctr))
+    if paths:
+        pc = np.zeros(len(DPLL_PATHS), dtype=np.int64)
+        st = lib().oracle_dpll_paths(*args, _p(pc, ctypes.c_int64), len(pc))
+        if st == -3:
+            raise RuntimeError("oracle_dpll_paths: DPLL_PATHS does not match the library's counters")
+    else:
+        st = lib().oracle_dpll(*args)
     nsol = min(ctr.solutions, sol_cap)
     sols = [sol_lits[sol_off[k]:sol_off[k + 1]].tolist() for k in range(nsol)]
-    return {"status": st, "solutions": sols,
-            "counters": {n: getattr(ctr, n) for n, _ in Counters._fields_},
-            "root_assign": root[:root_len.value].tolist()}
+    out = {"status": st, "solutions": sols,
+           "counters": {n: getattr(ctr, n) for n, _ in Counters._fields_},
+           "root_assign": root[:root_len.value].tolist()}
+    if paths:
+        out["paths"] = dict(zip(DPLL_PATHS, pc.tolist()))
+    return out
 
 
 def dp(formula, step_limit=0, clause_limit=0, record=False, rec_cap=1 << 20):

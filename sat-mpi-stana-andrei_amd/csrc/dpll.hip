@@ -995,6 +995,19 @@ static bool make_wide_layout(int max_vars, int max_clauses, int max_lits, DpllLa
     return true;
 }
 
+// Which storage form the general kernel takes: the wide form when it is pinned,
+// when the sizes pass the LDS layout (*lay is filled otherwise), and when a
+// clause is longer than the LDS form's clause word counts (Narrow::MAX_LEN) --
+// unless the LDS form is pinned, whose kernel then answers
+// SATMI_DPLL_TOO_LARGE for the instances that hold such a clause.
+// max_clause_len = 0 (unknown) plans by the sizes alone.
+static bool takes_wide(int policy, int max_vars, int max_clauses, int max_lits, int max_clause_len,
+                       DpllLayout *lay) {
+    if (policy == SATMI_KERNEL_WIDE) return true;
+    if (policy != SATMI_KERNEL_GENERAL && max_clause_len > Narrow::MAX_LEN) return true;
+    return !make_layout(max_vars, max_clauses, max_lits, lay);
+}
+
 // The launch state of every (device, stream) that ran a DPLL batch (DpllStream,
 // host.h).  The mutex guards the map only: a stream's state is used by the
 // caller launching on that stream.  Never destroyed: no hipFree after the
@@ -1162,7 +1175,7 @@ extern "C" int satmi_dpll_plan(int max_vars, int max_clauses, int max_lits, int 
         return rc;
     }
     DpllLayout lay;
-    if (policy == SATMI_KERNEL_WIDE || !make_layout(max_vars, max_clauses, max_lits, &lay)) {
+    if (takes_wide(policy, max_vars, max_clauses, max_lits, max_clause_len, &lay)) {
         if (!make_wide_layout(max_vars, max_clauses, max_lits, &lay)) {
             set_error("satmi_dpll_plan: instance too large for the wide (HBM arena) layout");
             return SATMI_ERR_TOO_LARGE;
@@ -1236,7 +1249,7 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
         return SATMI_ERR_ARG;
     }
     DpllLayout lay;
-    const bool wide = !scan_ok && (policy == SATMI_KERNEL_WIDE || !make_layout(max_vars, max_clauses, max_lits, &lay));
+    const bool wide = !scan_ok && takes_wide(policy, max_vars, max_clauses, max_lits, max_clause_len, &lay);
     if (wide && !make_wide_layout(max_vars, max_clauses, max_lits, &lay)) {
         set_error("satmi_dpll_batch_device: instance too large (wide layout: vars < 2^30, clauses <= 2^28, "
                   "literals <= 2^30, < 4 GiB per wave)");
@@ -1355,8 +1368,10 @@ extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_cl
         max_len = std::max(max_len, len);
         min_len = std::min(min_len, len);
     }
-    // the scan kernel needs every clause non-empty: report 0 (unknown) otherwise
-    const int max_clause_len = (C > 0 && min_len >= 1) ? max_len : 0;
+    // the scan kernel needs every clause non-empty: report 0 (unknown) otherwise.
+    // Past 5 literals no clause kernel is eligible, and the true length is what
+    // keeps a long clause beside an empty one out of the LDS form.
+    const int max_clause_len = (C > 0 && (min_len >= 1 || max_len > 5)) ? max_len : 0;
     for (int b = 0; b < num_instances; ++b) {
         const int cb = h_inst_clause_begin[b], ce = h_inst_clause_begin[b + 1];
         max_clauses = std::max(max_clauses, ce - cb);

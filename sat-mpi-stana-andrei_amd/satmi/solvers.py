@@ -82,6 +82,8 @@ def dpll_solve(formula: Formula):
     st = int(r.status[0])
     if st == _capi.DPLL_TIMEOUT:
         raise SolverTimeout(f"Timeout after {_time_limit:g} seconds")
+    if st not in (_capi.DPLL_EXHAUSTED, _capi.DPLL_STOPPED):   # nothing was decided: never an UNSAT verdict
+        raise _capi.SatmiError(f"dpll_solve: GPU search ended with status {_capi.STATUS_NAMES.get(st, st)}")
     if r.num_solutions(0) > 0:
         return True, {abs(l): l > 0 for l in r.solutions(0)[0]}
     return False, None

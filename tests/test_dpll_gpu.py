@@ -713,6 +713,11 @@ def test_wide_kernel_matches_general_and_oracle(seed, nmax, kmax, mmax):
             assert (rw.status == rg.status).all()
             assert (rw.counters[:, :7] == rg.counters[:, :7]).all()
             assert (rw.root_len == rg.root_len).all()
+        else:   # AUTO takes the wide form for the long clauses by itself
+            ra = dpll_batch(fs, mode=mode, max_solutions=maxs, sol_cap=cap, node_limit=3000)
+            assert (ra.status == rw.status).all() and (ra.counters[:, :7] == rw.counters[:, :7]).all()
+            for b in range(len(fs)):
+                assert ra.solutions(b) == rw.solutions(b) and ra.root_assignment(b) == rw.root_assignment(b), b
         for b in range(0, len(fs), 1 if long_clause else 5):
             o = oracle.dpll(fs[b], mode, max_solutions=maxs, node_limit=3000, sol_cap=cap)
             assert int(rw.status[b]) == o["status"], (mode, b)
