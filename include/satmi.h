@@ -243,6 +243,59 @@ int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const int32_t *h_li
                   int trace_cap, int32_t *h_steps, int32_t *h_rec_lits, int64_t rec_lit_cap,
                   int64_t *h_rec_clause_off, int64_t rec_clause_cap, int64_t *h_rec_step_off, int rec_step_cap);
 
+/*
+ * Batched Davis-Putnam elimination: many small clause sets in one launch, one
+ * workgroup per formula, every step of the elimination in LDS (CSR host arrays
+ * as satmi_resolution_batch_host).  A formula takes this path when
+ *   - it has at most 31 distinct variables (a clause is one key P | N << 32
+ *     over the dense variable index; the spare bit 31 keeps the all-ones word
+ *     from being a key, and key 0, the empty clause, is an ordinary clause);
+ *   - no clause list of its elimination, the input included, is longer than
+ *     the launch's capacity -- chosen from the batch: the smallest of 512 /
+ *     1,024 / 1,920 clauses that holds d x m for every formula of d <= 31
+ *     variables and m clauses, else 1,920;
+ *   - at every step the live variable ids have pairwise distinct home slots
+ *     id & (size - 1) in the table CPython builds for that many ids (8 slots
+ *     up to 4 ids, 32 up to 18, 128 up to 76): `variables.pop()` (REF.py:103)
+ *     then returns the id of the lowest home slot whatever the insertion
+ *     order, which is how the kernel orders the variables.
+ * Any other formula gets h_result[b] = SATMI_DP_BATCH_UNFIT and is left to
+ * satmi_dp_host; its h_steps[b] is 0 and its rows are zero, whatever progress
+ * was made.  There is no time limit: a formula's work is bounded by its capacity.
+ *   step_limit / clause_limit   <= 0: unlimited (satmi_dp_host's rules: the step
+ *                 limit is checked before the pop; the first event of a step in
+ *                 pair order decides between an empty resolvent, 0, and the
+ *                 resolvent that takes rest + resolvents over clause_limit, -1)
+ *   h_result[b], h_steps[b]     as satmi_dp_host's *result / *steps
+ *   h_trace_vars   [B x step_cap]: entry k = the variable eliminated at step k
+ *   h_step_clauses [B x step_cap]: entry k = the clause count after completed
+ *                 step k; zero-filled (the step that ended an elimination
+ *                 completed no list), exact for every step < step_cap
+ *   optional record (all three pointers or none; a part of them is an error):
+ *   the clause list after every completed step, formula after formula through
+ *   rec_clause_off / rec_lits; formula b's list after step k is clauses
+ *   rec_step_off[b * (step_cap + 1) + k] .. rec_step_off[b * (step_cap + 1) + k + 1],
+ *   in list order.  Every clause's literals are ascending by variable id (+v
+ *   before -v) -- NOT satmi_dp_host's set iteration order.  Truncation as
+ *   satmi_dp_host's record: a clause needs a free clause offset, literals past
+ *   rec_lit_cap are dropped.
+ * Arguments are checked before any HIP call (num_instances == 0 returns
+ * SATMI_OK).  Thread-safe like satmi_dp_host.
+ */
+#define SATMI_DP_BATCH_UNFIT (-2)
+int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                        const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                        int64_t step_limit, int64_t clause_limit,
+                        int32_t *h_result, int32_t *h_steps,
+                        int32_t *h_trace_vars, int64_t *h_step_clauses, int step_cap,
+                        int32_t *h_rec_lits, int64_t rec_lit_cap, int64_t *h_rec_clause_off,
+                        int64_t rec_clause_cap, int64_t *h_rec_step_off /* [B x (step_cap + 1)] */);
+
+/* Test knob of satmi_dp_batch_host (0 = default): at most `grid` workgroups
+ * are launched, and a clause list holds at most `clause_cap` clauses, so a few
+ * dozen tiny formulas exercise workgroup reuse and the UNFIT path. */
+int satmi_dp_debug_batch(int grid, int clause_cap);
+
 /* The floor of a chain of dependent kernel launches replayed from a HIP graph
  * on this device: `launches` one-block kernels captured in order on one
  * stream, the graph replayed `reps` times; *us_per_launch = the time per

@@ -22,6 +22,7 @@ STATUS_NAMES = {0: "exhausted", 1: "stopped", 2: "node_limit", 3: "timeout", 4: 
 RES_SAT, RES_UNSAT, RES_LIMIT = 1, 0, -1
 RES_BATCH_UNFIT = -2   # satmi_resolution_batch_host: the formula is left to satmi_resolution_host
 # satmi_resolution_last_regrowths: the words of its out array, in order
+DP_BATCH_UNFIT = -2    # satmi_dp_batch_host: the formula is left to satmi_dp_host
 RES_REGROWTHS = ("stage", "keys", "table", "chunks", "cand_reruns", "table_rebuilds", "clause_growths")
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_SCAN, KERNEL_INC, KERNEL_WIDE = 0, 1, 2, 3, 4
 
@@ -38,6 +39,7 @@ EXPORTED = (
     "satmi_dp_trim", "satmi_resolution_trim", "satmi_cdcl_last_stats", "satmi_launch_chain_floor",
     "satmi_dpll_split_busy", "satmi_dpll_scan_shape", "satmi_resolution_last_regrowths",
     "satmi_resolution_batch_host", "satmi_resolution_debug_batch",
+    "satmi_dp_batch_host", "satmi_dp_debug_batch",
 )
 
 
@@ -159,6 +161,10 @@ def load():
     L.satmi_dp_host.argtypes = [
         ctypes.c_int, i32p, i32p, ctypes.c_int64, ctypes.c_int64, ctypes.c_double, i32p, i32p, ctypes.c_int, i32p,
         i32p, ctypes.c_int64, i64p, ctypes.c_int64, i64p, ctypes.c_int]
+    L.satmi_dp_batch_host.argtypes = [
+        ctypes.c_int, i32p, i32p, i32p, ctypes.c_int64, ctypes.c_int64,
+        i32p, i32p, i32p, i64p, ctypes.c_int, i32p, ctypes.c_int64, i64p, ctypes.c_int64, i64p]
+    L.satmi_dp_debug_batch.argtypes = [ctypes.c_int, ctypes.c_int]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = library/header mismatch
     _lib = L

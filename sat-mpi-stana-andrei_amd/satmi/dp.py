@@ -1,9 +1,10 @@
-"""Davis-Putnam elimination on the GPU (libsatmi.so, csrc/dp.hip).
+"""Davis-Putnam elimination on the GPU (libsatmi.so, csrc/dp.hip, csrc/dp_batch.hip).
 
 `eliminate(formula, ...)` runs REF.py:98-130 step by step -- variables in the
 reference's own order (CPython's `set.pop()`, modelled on the device) -- and can
 return every intermediate clause list; `davis_putnam_solve` is the reference's
-boolean entry point.
+boolean entry point.  `eliminate_batch` / `davis_putnam_solve_batch` run many small
+formulas in one launch, one workgroup per formula.
 """
 import ctypes
 
@@ -74,3 +75,133 @@ def davis_putnam_solve(formula, time_limit=0.0):
     if r["result"] < 0:
         raise DavisPutnamLimit(f"Davis-Putnam stopped by its limit after {r['steps']} steps")
     return bool(r["result"])
+
+
+# ---------------------------------------------------------------- the batch
+_STEP_CAP = 64   # the device keeps rows for 64 steps: at most 31 variables, each popped at most twice
+
+
+def order_free_pop(ids):
+    """What `set(ids).pop()` returns for distinct small positive ints whatever
+    their insertion order, or None when the order decides.  A fresh set of n
+    such ints has 8 slots for n <= 4, 32 for n <= 18, 128 for n <= 76, ...
+    (CPython's growth rule); when the home slots `id & (slots - 1)` are
+    pairwise distinct every id sits at its home and pop() takes the lowest
+    home -- {3, 4, 5, 9} pops 9, {15, 16} pops 16.  With colliding homes
+    ({3, 11}) the insertion order decides: None.  The batched kernel orders
+    its variables by this rule (csrc/dp_batch.hip)."""
+    ids = list(ids)
+    n = len(ids)
+    if n == 0 or len(set(ids)) != n or min(ids) < 1:
+        return None
+    mask = 7
+    while True:
+        thr = (mask * 3 + 4) // 5            # the fill that triggers the next resize
+        if n < thr:
+            break
+        minused = thr * 2 if thr > 50000 else thr * 4
+        size = 8
+        while size <= minused:
+            size <<= 1
+        mask = size - 1
+    homes = {}
+    for v in ids:
+        if homes.setdefault(v & mask, v) != v:
+            return None
+    return homes[min(homes)]
+
+
+def debug_batch(grid=0, clause_cap=0):
+    """Test knob of eliminate_batch (satmi_dp_debug_batch; 0 = default): at most
+    `grid` workgroups, at most `clause_cap` clauses per clause list."""
+    _capi.check(_capi.load().satmi_dp_debug_batch(int(grid), int(clause_cap)), "satmi_dp_debug_batch")
+
+
+def _lit_order(clause):
+    """A clause in the batch record's literal order: ascending variable id, +v before -v."""
+    return sorted(set(clause), key=lambda l: (abs(l), l < 0))
+
+
+def eliminate_batch(formulas, step_limit=0, clause_limit=0, time_limit=0.0, record=False, rec_cap=1 << 20):
+    """eliminate() for many small formulas in one launch (csrc/dp_batch.hip: one
+    workgroup per formula, every step in LDS).  `formulas` is a list of formulas
+    or a cnf.CnfBatch; returns a list of eliminate()'s dicts, each with
+      "path": "batch", or "single" for a formula the batched kernel does not
+          take (more than 31 variables, a clause list beyond its capacity, or
+          live variable ids whose set-table homes collide: order_free_pop),
+          which is run through eliminate() -- `time_limit` applies to those
+          calls only: the batched kernel's work is bounded by its capacity;
+      "step_clauses": the clause count after every completed step (a step that
+          ended the elimination completed none).  For a "single" result it is
+          taken from the record when record=True and omitted otherwise;
+      "clauses" (record=True): the clause list after every completed step, in
+          list order, every clause's literals ascending by variable id (+v
+          before -v) -- not eliminate()'s set iteration order; "single"
+          results are normalised to the same order."""
+    from . import cnf
+    L = _capi.load()
+    if isinstance(formulas, cnf.CnfBatch):
+        cb = formulas
+    else:
+        formulas = list(formulas)
+        cb = cnf.pack(formulas) if formulas else None
+    if cb is None or cb.num_instances == 0:
+        return []
+    _capi.require_gpu()
+    B = cb.num_instances
+    res = np.zeros(B, dtype=np.int32)
+    steps = np.zeros(B, dtype=np.int32)
+    trace = np.zeros((B, _STEP_CAP), dtype=np.int32)
+    sc = np.zeros((B, _STEP_CAP), dtype=np.int64)
+    icb, clb, lits = (np.ascontiguousarray(a, dtype=np.int32)
+                      for a in (cb.inst_clause_begin, cb.clause_lit_begin, cb.lits))
+    i64 = ctypes.c_int64
+    args = (B, _p(icb), _p(clb), _p(lits), int(step_limit), int(clause_limit), _p(res), _p(steps), _p(trace),
+            _p(sc, i64), _STEP_CAP)
+    if not record:
+        _capi.check(L.satmi_dp_batch_host(*args, None, 0, None, 0, None), "satmi_dp_batch_host")
+    else:
+        while True:
+            rl = np.zeros(rec_cap, dtype=np.int32)
+            rco = np.zeros(rec_cap + 1, dtype=np.int64)
+            rso = np.zeros((B, _STEP_CAP + 1), dtype=np.int64)
+            _capi.check(L.satmi_dp_batch_host(*args, _p(rl), rec_cap, _p(rco, i64), rec_cap + 1, _p(rso, i64)),
+                        "satmi_dp_batch_host")
+            # the record is truncated silently at its capacities: complete iff it
+            # holds every counted clause and the literals did not run out
+            if int(rso[-1, -1]) == int(sc.sum()) and int(rco[int(rso[-1, -1])]) < rec_cap:
+                break
+            rec_cap *= 4
+    out = []
+    for b in range(B):
+        if res[b] == _capi.DP_BATCH_UNFIT:
+            r = eliminate(cb.instance(b), step_limit=step_limit, clause_limit=clause_limit, time_limit=time_limit,
+                          record=record)
+            if record:
+                r["clauses"] = [[_lit_order(c) for c in cl] for cl in r["clauses"]]
+                r["step_clauses"] = [len(cl) for cl in r["clauses"]]
+            r["path"] = "single"
+        else:
+            n = int(steps[b])
+            # a completed list is empty only when it ends the elimination with
+            # True, so a last step with count 0 under another verdict is the
+            # step that ended it
+            done = n if n == 0 or res[b] == 1 or sc[b, n - 1] > 0 else n - 1
+            r = {"result": int(res[b]), "vars": trace[b, :n].tolist(), "steps": n,
+                 "step_clauses": sc[b, :done].tolist()}
+            if record:
+                r["clauses"] = [[rl[rco[c]:rco[c + 1]].tolist() for c in range(rso[b, k], rso[b, k + 1])]
+                                for k in range(done)]
+            r["path"] = "batch"
+        out.append(r)
+    return out
+
+
+def davis_putnam_solve_batch(formulas, time_limit=0.0):
+    """davis_putnam_solve for a list of formulas (or a cnf.CnfBatch) -> List[bool]."""
+    out = []
+    for r in eliminate_batch(formulas, time_limit=time_limit):
+        if r["result"] < 0:
+            raise DavisPutnamLimit(f"Davis-Putnam stopped by its limit after {r['steps']} steps")
+        out.append(bool(r["result"]))
+    return out

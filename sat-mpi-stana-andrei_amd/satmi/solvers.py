@@ -106,6 +106,13 @@ def davis_putnam_solver(formula: Formula) -> bool:
     return davis_putnam_solve(formula, time_limit=_time_limit)
 
 
+def davis_putnam_solver_batch(formulas: List[Formula]) -> List[bool]:
+    """davis_putnam_solver for many formulas in one launch (small formulas are
+    eliminated one per workgroup; the others go through davis_putnam_solver's path)."""
+    from .dp import davis_putnam_solve_batch
+    return davis_putnam_solve_batch(formulas, time_limit=_time_limit)
+
+
 def pysat_solver(formula: Formula) -> List[Assignment]:
     """REF.py:387-397 delegates to PySAT's Glucose3, a third-party library that
     is not part of this image.  It is used when installed; otherwise this raises."""
