@@ -46,9 +46,11 @@
 // a step whose live ids collide makes the formula UNFIT (the order is then not
 // recoverable from the keys).
 //
-// The split, the resolvent and the filter restate dp.hip's; its kernels are
-// not edited so their machine code stays what the bench's rooflines are keyed
-// by.
+// The host side is shared with resolution_batch.hip: the check, the encoder and
+// the decoder are batch_keys.h's, the workspace, the carving of the blocks and
+// the grid size batch_host.h's.  The kernel's split, resolvent and filter
+// restate dp.hip's: device code is not shared, so those kernels' machine code,
+// which the bench's rooflines are keyed by, stays what it is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,13 +60,13 @@
 #include <string>
 #include <vector>
 
+#include "batch_host.h"
 #include "common.h"
-#include "host.h"
 
 namespace satmi {
 
 constexpr int DPB_CHUNK = 1024;      // pairs per chunk
-constexpr int DPB_MAXVARS = 31;      // distinct variables of a formula
+constexpr int DPB_MAXVARS = BATCH_MAXVARS;   // distinct variables of a formula
 constexpr int DPB_STEPS_MAX = 64;    // steps the device keeps rows for: a variable is popped at most twice
 constexpr int DPB_NOEVENT = INT_MAX;
 
@@ -354,41 +356,11 @@ constexpr Tier DPB_TIERS[] = {
 };
 constexpr int DPB_NTIERS = (int)(sizeof(DPB_TIERS) / sizeof(DPB_TIERS[0]));
 constexpr int DPB_CLAUSE_CAP_MAX = DPB_TIERS[DPB_NTIERS - 1].clause_cap;
-constexpr size_t DPB_LDS_PER_CU = 160 * 1024;
+constexpr size_t DPB_LDS_SLACK = 512;   // static LDS of a workgroup, rounded up
 
 std::atomic<int> g_dbg_grid{0}, g_dbg_cap{0};   // satmi_dp_debug_batch
 
-struct DpbPin {   // pinned host memory, grow-only
-    unsigned char *p = nullptr;
-    size_t cap = 0;
-    ~DpbPin() {
-        if (p) (void)hipHostFree(p);
-    }
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SATMI_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(bytes + bytes / 2, (size_t)4096);
-        SATMI_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-        cap = want;
-        return SATMI_OK;
-    }
-};
-
-// A call's device state, kept between calls in the workspace pool (host.h).
-// Nothing in it is trusted by the next call (inputs are uploaded, outputs
-// zeroed, every call), so it goes back to the pool whatever the outcome.
-struct DpBatchWork {
-    DevBuf up, out, keys_out, rec_off;
-    DpbPin up_h, out_h;
-    hipStream_t stream = nullptr;
-    int dev = 0;
-    ~DpBatchWork() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    bool open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
-};
+struct DpBatchWork : BatchWork {};   // a pool of its own
 
 int fail_arg(const char *what) {
     set_error(std::string("satmi_dp_batch_host: ") + what);
@@ -416,87 +388,26 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
                                    int64_t clause_limit, int32_t *h_result, int32_t *h_steps, int32_t *h_trace_vars,
                                    int64_t *h_step_clauses, int step_cap, int32_t *h_rec_lits, int64_t rec_lit_cap,
                                    int64_t *h_rec_clause_off, int64_t rec_clause_cap, int64_t *h_rec_step_off) {
-    // ---- validation: all of it before any HIP call
-    if (num_instances < 0) return fail_arg("negative formula count");
-    if (step_cap < 0) return fail_arg("step_cap < 0");
+    // ---- check: all of it before any HIP call
     const int nrec = (h_rec_lits != nullptr) + (h_rec_clause_off != nullptr) + (h_rec_step_off != nullptr);
-    if (nrec != 0 && nrec != 3) return fail_arg("the record needs all of its pointers or none");
     const bool record = nrec == 3;
-    if (record && (rec_lit_cap < 0 || rec_clause_cap < 0)) return fail_arg("negative record capacity");
+    const char *own = nullptr;   // this entry point's own arguments, behind the count
+    if (step_cap < 0) own = "step_cap < 0";
+    else if (nrec != 0 && nrec != 3) own = "the record needs all of its pointers or none";
+    else if (record && (rec_lit_cap < 0 || rec_clause_cap < 0)) own = "negative record capacity";
+    if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits, own,
+                                          h_result && h_steps && (step_cap <= 0 || (h_trace_vars && h_step_clauses))))
+        return fail_arg(bad);
     if (num_instances == 0) return SATMI_OK;
     const int B = num_instances;
-    if (!h_inst_clause_begin || !h_clause_lit_begin || !h_result || !h_steps ||
-        (step_cap > 0 && (!h_trace_vars || !h_step_clauses)))
-        return fail_arg("null pointer");
-    if (h_inst_clause_begin[0] < 0) return fail_arg("clause ranges are not ascending");
-    for (int b = 0; b < B; ++b)
-        if (h_inst_clause_begin[b + 1] < h_inst_clause_begin[b]) return fail_arg("clause ranges are not ascending");
-    const int C = h_inst_clause_begin[B];
-    if (h_clause_lit_begin[0] < 0) return fail_arg("literal ranges are not ascending");
-    for (int c = 0; c < C; ++c)
-        if (h_clause_lit_begin[c + 1] < h_clause_lit_begin[c]) return fail_arg("literal ranges are not ascending");
-    const int64_t Ltot = h_clause_lit_begin[C];
-    if (Ltot > 0 && !h_lits) return fail_arg("null pointer");
-    {
-        int bad = 0;
-        for (int64_t j = h_clause_lit_begin[0]; j < Ltot; ++j) bad |= (h_lits[j] == 0) | (h_lits[j] == INT32_MIN);
-        if (bad) return fail_arg("literal 0 / INT32_MIN");
-    }
 
-    // ---- the dense variable index of every formula (variables in ascending
-    // order of their ids, as host.h's dense_var_index numbers them) and the
-    // input keys P | N << 32: a repeated literal is one bit, a tautological
-    // clause keeps both of its bits, the empty clause is key 0
-    std::vector<int32_t> nv((size_t)B, 0), d2v((size_t)B * 32, 0), vars;
-    std::vector<uint64_t> keys((size_t)std::max(C, 1), 0ull);
-    int64_t need = 1;   // max over the formulas that can fit of d x m
-    for (int b = 0; b < B; ++b) {
-        const int cb = h_inst_clause_begin[b], ce = h_inst_clause_begin[b + 1];
-        const int64_t lb = h_clause_lit_begin[cb], le = h_clause_lit_begin[ce];
-        int32_t *dv = d2v.data() + (size_t)b * 32;
-        uint32_t mv = 0;
-        for (int64_t j = lb; j < le; ++j) mv = std::max(mv, (uint32_t)std::abs(h_lits[j]));
-        int d;
-        if (mv <= 63) {   // the common case: the variable set is one word
-            uint64_t used = 0;
-            for (int64_t j = lb; j < le; ++j) used |= 1ull << std::abs(h_lits[j]);
-            d = __builtin_popcountll(used);
-            if (d <= DPB_MAXVARS) {
-                for (int c = cb; c < ce; ++c) {
-                    uint64_t k = 0;
-                    for (int64_t j = h_clause_lit_begin[c]; j < h_clause_lit_begin[c + 1]; ++j) {
-                        const int x = h_lits[j], v = std::abs(x);
-                        const int idx = __builtin_popcountll(used & ((1ull << v) - 1ull));
-                        k |= 1ull << (idx + (x < 0 ? 32 : 0));
-                    }
-                    keys[(size_t)c] = k;
-                }
-                int n = 0;
-                for (int v = 1; v <= 63; ++v)
-                    if ((used >> v) & 1ull) dv[n++] = v;
-            }
-        } else {
-            vars.clear();
-            for (int64_t j = lb; j < le; ++j) vars.push_back(std::abs(h_lits[j]));
-            std::sort(vars.begin(), vars.end());
-            vars.erase(std::unique(vars.begin(), vars.end()), vars.end());
-            d = (int)std::min<size_t>(vars.size(), 1 << 20);
-            if (d <= DPB_MAXVARS) {
-                for (int c = cb; c < ce; ++c) {
-                    uint64_t k = 0;
-                    for (int64_t j = h_clause_lit_begin[c]; j < h_clause_lit_begin[c + 1]; ++j) {
-                        const int x = h_lits[j];
-                        const int idx = (int)(std::lower_bound(vars.begin(), vars.end(), std::abs(x)) - vars.begin());
-                        k |= 1ull << (idx + (x < 0 ? 32 : 0));
-                    }
-                    keys[(size_t)c] = k;
-                }
-                std::copy(vars.begin(), vars.end(), dv);
-            }
-        }
-        nv[(size_t)b] = d;
-        if (d <= DPB_MAXVARS) need = std::max<int64_t>(need, (int64_t)d * (ce - cb));
-    }
+    // ---- encode; the tier: the smallest that holds d x m clauses for every formula that can fit
+    BatchKeys K;
+    batch_encode(B, h_inst_clause_begin, h_clause_lit_begin, h_lits, &K);
+    int64_t need = 1;
+    for (int b = 0; b < B; ++b)
+        if (K.nvars[(size_t)b] <= DPB_MAXVARS)
+            need = std::max<int64_t>(need, (int64_t)K.nvars[(size_t)b] * (h_inst_clause_begin[b + 1] - h_inst_clause_begin[b]));
     Tier tier = DPB_TIERS[DPB_NTIERS - 1];
     for (int t = DPB_NTIERS - 1; t >= 0; --t)
         if (need <= DPB_TIERS[t].clause_cap) tier = DPB_TIERS[t];
@@ -506,7 +417,7 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
     const int PC = std::min(step_cap, DPB_STEPS_MAX);   // rows the device keeps per formula
     const size_t PCa = (size_t)std::max(PC, 1);
 
-    // ---- the workspace
+    // ---- lease the workspace
     int dev = 0;
     DeviceFacts facts;
     SATMI_TRY(device_facts(&facts, &dev));
@@ -515,29 +426,30 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
         set_error("satmi_dp_batch_host: hipStreamCreate failed");
         return SATMI_ERR_HIP;
     }
-    lease.ok = true;   // whatever the call's outcome (see DpBatchWork)
+    lease.ok = true;   // whatever the call's outcome (see BatchWork)
     DpBatchWork &wk = *lease.w;
     hipStream_t s = wk.stream;
-    const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // inputs, one copy: clause ranges, variable counts, index -> id, keys
-    const size_t u_nv = al(4 * (size_t)(B + 1)), u_d2v = u_nv + al(4 * (size_t)B);
-    const size_t u_keys = u_d2v + al(128 * (size_t)B), up_bytes = u_keys + al(8 * (size_t)std::max(C, 1));
+    // ---- carve.  Inputs, one copy: clause ranges, variable counts, index -> id, keys
+    Carve cu;
+    const size_t u_icb = cu.take(4 * (size_t)(B + 1)), u_nv = cu.take(4 * (size_t)B);
+    const size_t u_d2v = cu.take(4 * K.d2v.size()), u_keys = cu.take(8 * K.keys.size()), up_bytes = cu.at;
     // outputs, zeroed, one copy back: work word, results, steps, trace rows, clause-count rows
-    const size_t o_res = 256, o_stp = o_res + al(4 * (size_t)B), o_trc = o_stp + al(4 * (size_t)B);
-    const size_t o_sc = o_trc + al(4 * (size_t)B * PCa), out_bytes = o_sc + al(8 * (size_t)B * PCa);
+    Carve co;
+    const size_t o_work = co.take(4), o_res = co.take(4 * (size_t)B), o_stp = co.take(4 * (size_t)B);
+    const size_t o_trc = co.take(4 * (size_t)B * PCa), o_sc = co.take(8 * (size_t)B * PCa), out_bytes = co.at;
     SATMI_TRY(wk.up.reserve(up_bytes, &DPB_OOM));
     SATMI_TRY(wk.out.reserve(out_bytes, &DPB_OOM));
-    SATMI_TRY(wk.up_h.reserve(up_bytes));
-    SATMI_TRY(wk.out_h.reserve(out_bytes));
-    std::memcpy(wk.up_h.p, h_inst_clause_begin, 4 * (size_t)(B + 1));
-    std::memcpy(wk.up_h.p + u_nv, nv.data(), 4 * (size_t)B);
-    std::memcpy(wk.up_h.p + u_d2v, d2v.data(), 128 * (size_t)B);
-    std::memcpy(wk.up_h.p + u_keys, keys.data(), 8 * (size_t)std::max(C, 1));
+    SATMI_TRY(wk.up_h.grow(up_bytes));
+    SATMI_TRY(wk.out_h.grow(out_bytes));
+    std::memcpy(wk.up_h.p + u_icb, h_inst_clause_begin, 4 * (size_t)(B + 1));
+    std::memcpy(wk.up_h.p + u_nv, K.nvars.data(), 4 * (size_t)B);
+    std::memcpy(wk.up_h.p + u_d2v, K.d2v.data(), 4 * K.d2v.size());
+    std::memcpy(wk.up_h.p + u_keys, K.keys.data(), 8 * K.keys.size());
     SATMI_HIP(hipMemcpyAsync(wk.up.p, wk.up_h.p, up_bytes, hipMemcpyHostToDevice, s));
 
     unsigned char *up = wk.up.as<unsigned char>(), *out = wk.out.as<unsigned char>();
     DpBatchArgs A;
-    A.icb = (const int32_t *)up;
+    A.icb = (const int32_t *)(up + u_icb);
     A.nvars = (const int32_t *)(up + u_nv);
     A.d2v = (const int32_t *)(up + u_d2v);
     A.keys_in = (const uint64_t *)(up + u_keys);
@@ -552,20 +464,16 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
     A.step_cap = PC;
     A.keys_out = nullptr;
     A.rec_off = nullptr;
-    A.work = (uint32_t *)out;
-    // a persistent grid: the workgroups a CU holds by LDS and by its 32 wave slots
+    A.work = (uint32_t *)(out + o_work);
+
+    // ---- launch: one persistent grid, a second time when the record is kept
     int threads = B <= facts.cus ? tier.threads_few : tier.threads;
     if (const char *e = std::getenv("SATMI_DP_BATCH_WIDTH")) {   // measurement knob (tools/dp_batch_time.py --sweep)
         const int w = std::atoi(e);
         if (w >= 64 && w <= 1024 && w % 64 == 0) threads = w;
     }
-    const int waves = threads / 64;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({DPB_LDS_PER_CU / (lds_bytes + 512), (size_t)(32 / waves), 16}));
-    int grid = (int)std::min<int64_t>(B, (int64_t)facts.cus * per_cu);
-    if (dbg_grid > 0) grid = std::min(grid, dbg_grid);
-    if (lds_bytes > 48 * 1024)
-        SATMI_HIP(hipFuncSetAttribute((const void *)dp_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds_bytes));
+    const int grid = batch_grid(facts, lds_bytes, DPB_LDS_SLACK, threads, B, dbg_grid);
+    SATMI_TRY(batch_allow_lds((const void *)dp_batch_kernel, lds_bytes));
     const auto launch = [&]() -> int {
         SATMI_HIP(hipMemsetAsync(wk.out.p, 0, out_bytes, s));
         hipLaunchKernelGGL(dp_batch_kernel, dim3(grid), dim3(threads), lds_bytes, s, A);
@@ -606,12 +514,11 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
             hk.resize((size_t)nkeys);
             SATMI_HIP(hipMemcpyAsync(hk.data(), wk.keys_out.p, 8 * (size_t)nkeys, hipMemcpyDeviceToHost, s));
             SATMI_HIP(hipStreamSynchronize(s));
-            // (not kept in the pool past a large recorded batch)
-            if (wk.keys_out.cap > ((size_t)64 << 20)) wk.keys_out.release();
+            wk.drop_large_record();
         }
     }
 
-    // ---- results
+    // ---- copy back
     for (int b = 0; b < B; ++b) {
         const bool unfit = r_res[b] == SATMI_DP_BATCH_UNFIT;
         h_result[b] = r_res[b];
@@ -630,7 +537,7 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
     }
     if (!record) return SATMI_OK;
 
-    // ---- the record decoded: formula after formula, the list after every
+    // ---- decode the record: formula after formula, the list after every
     // completed step, clauses in list order, literals ascending by variable id
     // (+v before -v), with satmi_dp_host's truncation: a clause needs a free
     // clause offset, a literal past rec_lit_cap is dropped
@@ -641,19 +548,18 @@ extern "C" int satmi_dp_batch_host(int num_instances, const int32_t *h_inst_clau
         srow[0] = rec_clauses;
         const bool unfit = r_res[b] == SATMI_DP_BATCH_UNFIT;
         const int ns = unfit ? 0 : std::min(r_stp[b], PC);
-        const int32_t *dv = d2v.data() + (size_t)b * 32;
-        const int V = std::min(nv[(size_t)b], 32);
+        const int32_t *dv = K.d2v.data() + (size_t)b * BATCH_D2V_STRIDE;
+        const int V = std::min(K.nvars[(size_t)b], BATCH_D2V_STRIDE);
         int64_t at = roff[(size_t)b];
         const int64_t end = roff[(size_t)b + 1];
         for (int k = 0; k < ns; ++k) {
             // (the step that ended the elimination completed no list: its count is 0)
             const int64_t n = r_sc[(size_t)b * PCa + k];
             for (int64_t c = 0; c < n && at < end && rec_clauses + 1 < rec_clause_cap; ++c, ++at) {
-                const uint64_t key = hk[(size_t)at];
-                for (int i = 0; i < V; ++i) {
-                    if (((key >> i) & 1ull) && rec_lits < rec_lit_cap) h_rec_lits[rec_lits++] = dv[i];
-                    if (((key >> (32 + i)) & 1ull) && rec_lits < rec_lit_cap) h_rec_lits[rec_lits++] = -dv[i];
-                }
+                int32_t cl[64];
+                const int64_t nl = std::min<int64_t>(batch_decode(hk[(size_t)at], dv, V, cl), rec_lit_cap - rec_lits);
+                std::copy(cl, cl + nl, h_rec_lits + rec_lits);
+                rec_lits += nl;
                 h_rec_clause_off[++rec_clauses] = rec_lits;
             }
             srow[k + 1] = rec_clauses;

@@ -1,8 +1,10 @@
 // host.h -- the host-side layer the solver translation units share (dpll.hip,
-// dpll_scan.hip, dp.hip, resolution.hip, cdcl.hip): the error-propagating
-// SATMI_TRY, the cached device facts, the grow-only device buffer, the
-// workspace pool with its lease, the dense variable index, and the DPLL
-// launches' per-stream state.  Host code only; device helpers are in common.h.
+// dpll_scan.hip, dp.hip, resolution.hip, cdcl.hip, resolution_batch.hip,
+// dp_batch.hip): the error-propagating SATMI_TRY, the cached device facts, the
+// grow-only device and pinned buffers, the workspace pool with its lease, the
+// dense variable index, and the DPLL launches' per-stream state (the two batched
+// entry points share batch_keys.h and batch_host.h besides).  Host code only;
+// device helpers are in common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,6 +117,33 @@ private:
         SATMI_HIP(hipMalloc(np, want));
         return SATMI_OK;
     }
+};
+
+// Grow-only pinned host memory (contents lost on regrowth): a call's inputs
+// are gathered here and sent in one copy (a copy from pageable memory is staged
+// synchronously, one per array), and small results come back through it.
+// `reserve` allocates exactly what is asked, `grow` half as much again.
+struct PinBuf {
+    unsigned char *p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf &) = delete;
+    PinBuf &operator=(const PinBuf &) = delete;
+    ~PinBuf() { release(); }
+    void release() {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    int reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
+        if (bytes <= cap) return SATMI_OK;
+        release();
+        const size_t want = std::max<size_t>(bytes, 4096);
+        SATMI_HIP(hipHostMalloc((void **)&p, want, flags));
+        cap = want;
+        return SATMI_OK;
+    }
+    int grow(size_t bytes) { return bytes <= cap ? SATMI_OK : reserve(bytes + bytes / 2); }
 };
 
 // ---------------------------------------------------------------- workspace pool

@@ -706,27 +706,6 @@ namespace {
 // freed before they are regrown, to exactly what is asked (DevBuf::reserve).
 constexpr OomText RES_OOM{"satmi_resolution_host", "bound the saturation with clause_limit / max_passes"};
 
-// Pinned host memory, grow-only: the call's inputs are gathered here and sent
-// in one copy (a copy from pageable memory is staged synchronously, one per
-// array), and small results come back through it.
-struct PinBuf {
-    unsigned char *p = nullptr;
-    size_t cap = 0;
-    ~PinBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    int reserve(size_t bytes, unsigned flags = hipHostMallocDefault) {
-        if (bytes <= cap) return SATMI_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(bytes, (size_t)4096);
-        SATMI_HIP(hipHostMalloc((void **)&p, want, flags));
-        cap = want;
-        return SATMI_OK;
-    }
-};
-
 uint64_t table_slots(int64_t keys) {
     uint64_t cap = 1024;
     while (cap < 2 * (uint64_t)keys) cap <<= 1;

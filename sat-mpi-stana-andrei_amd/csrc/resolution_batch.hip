@@ -26,14 +26,14 @@
 //     SATMI_RES_BATCH_UNFIT and the workgroup goes on: appends past key_cap are
 //     counted, never stored, and a probe run is bounded by the table size.
 //
-// The host builds the dense index and the keys (a batch of 4,096 formulas is
-// ~600 k literals), uploads them in one copy, and decodes the optional record
-// from the keys the kernel leaves in HBM.
+// The host checks the batch, builds the dense index and the keys (a batch of
+// 4,096 formulas is ~600 k literals), uploads them in one copy, and decodes the
+// optional record from the keys the kernel leaves in HBM; that host side is
+// shared with dp_batch.hip (batch_keys.h, batch_host.h).
 //
-// The pair classification restates res_pass_packed_kernel's (resolution.hip):
-// that kernel spells it inline, and moving it into a shared header would have
-// meant editing resolution.hip, whose text tests/res_paths.py reads and whose
-// machine code the bench's issue rooflines are keyed by.
+// The kernel's pair classification restates res_pass_packed_kernel's
+// (resolution.hip): device code is not shared, so that kernel's machine code,
+// which the bench's issue rooflines are keyed by, stays what it is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,8 +42,8 @@
 #include <string>
 #include <vector>
 
+#include "batch_host.h"
 #include "common.h"
-#include "host.h"
 
 namespace satmi {
 
@@ -250,41 +250,11 @@ constexpr Tier RB_TIERS[] = {
 };
 constexpr int RB_NTIERS = (int)(sizeof(RB_TIERS) / sizeof(RB_TIERS[0]));
 constexpr int RB_KEY_CAP_MAX = RB_TIERS[RB_NTIERS - 1].key_cap;
-constexpr size_t RB_LDS_PER_CU = 160 * 1024;
+constexpr size_t RB_LDS_SLACK = 64;   // static LDS of a workgroup, rounded up
 
 std::atomic<int> g_dbg_grid{0}, g_dbg_key_cap{0};   // satmi_resolution_debug_batch
 
-struct RbPin {   // pinned host memory, grow-only
-    unsigned char *p = nullptr;
-    size_t cap = 0;
-    ~RbPin() {
-        if (p) (void)hipHostFree(p);
-    }
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return SATMI_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(bytes + bytes / 2, (size_t)4096);
-        SATMI_HIP(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-        cap = want;
-        return SATMI_OK;
-    }
-};
-
-// A call's device state, kept between calls in the workspace pool (host.h).
-// Nothing in it is trusted by the next call (inputs are uploaded, outputs
-// zeroed, every call), so it goes back to the pool whatever the outcome.
-struct ResBatchWork {
-    DevBuf up, out, keys_out;
-    RbPin up_h, out_h;
-    hipStream_t stream = nullptr;
-    int dev = 0;
-    ~ResBatchWork() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    bool open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
-};
+struct ResBatchWork : BatchWork {};   // a pool of its own (rec_off stays empty)
 
 int fail_arg(const char *what) {
     set_error(std::string("satmi_resolution_batch_host: ") + what);
@@ -313,87 +283,25 @@ extern "C" int satmi_resolution_batch_host(int num_instances, const int32_t *h_i
                                            int32_t *h_passes, int64_t *h_pass_new, int pass_cap, int32_t *h_rec_lits,
                                            int64_t rec_lit_cap, int64_t *h_rec_clause_off, int64_t rec_clause_cap,
                                            int64_t *h_rec_pass_off) {
-    // ---- validation: all of it before any HIP call
-    if (num_instances < 0) return fail_arg("negative formula count");
-    if (pass_cap < 0) return fail_arg("pass_cap < 0");
+    // ---- check: all of it before any HIP call
+    if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits,
+                                          pass_cap < 0 ? "pass_cap < 0" : nullptr,
+                                          h_result && h_passes && (pass_cap <= 0 || h_pass_new)))
+        return fail_arg(bad);
     if (num_instances == 0) return SATMI_OK;
     const int B = num_instances;
-    if (!h_inst_clause_begin || !h_clause_lit_begin || !h_result || !h_passes || (pass_cap > 0 && !h_pass_new))
-        return fail_arg("null pointer");
-    if (h_inst_clause_begin[0] < 0) return fail_arg("clause ranges are not ascending");
-    for (int b = 0; b < B; ++b)
-        if (h_inst_clause_begin[b + 1] < h_inst_clause_begin[b]) return fail_arg("clause ranges are not ascending");
-    const int C = h_inst_clause_begin[B];
-    if (h_clause_lit_begin[0] < 0) return fail_arg("literal ranges are not ascending");
-    for (int c = 0; c < C; ++c)
-        if (h_clause_lit_begin[c + 1] < h_clause_lit_begin[c]) return fail_arg("literal ranges are not ascending");
-    const int64_t Ltot = h_clause_lit_begin[C];
-    if (Ltot > 0 && !h_lits) return fail_arg("null pointer");
-    {
-        int bad = 0;
-        for (int64_t j = h_clause_lit_begin[0]; j < Ltot; ++j) bad |= (h_lits[j] == 0) | (h_lits[j] == INT32_MIN);
-        if (bad) return fail_arg("literal 0 / INT32_MIN");
-    }
-    const bool record = h_rec_lits && h_rec_clause_off && h_rec_pass_off;
+    const bool record = h_rec_lits && h_rec_clause_off && h_rec_pass_off;   // (a partial set: no record)
 
-    // ---- the dense variable index of every formula (variables in ascending
-    // order of their ids, as host.h's dense_var_index numbers them) and the
-    // input keys P | N << 32: a repeated literal is one bit, a tautological
-    // clause keeps both of its bits, the empty clause is key 0
-    std::vector<int32_t> nv((size_t)B, 0);
-    std::vector<uint64_t> keys((size_t)std::max(C, 1), 0ull);
-    std::vector<int32_t> d2v;             // the formulas' dense2var lists, one after another (record only)
-    std::vector<int64_t> d2v_off((size_t)B + 1, 0);
-    std::vector<int32_t> vars;
-    int64_t need = 1;                     // max over the formulas that can fit of 3^d + m
+    // ---- encode; the tier: the smallest that holds 3^d + m keys for every formula that can fit
+    BatchKeys K;
+    batch_encode(B, h_inst_clause_begin, h_clause_lit_begin, h_lits, &K);
+    int64_t need = 1;
     for (int b = 0; b < B; ++b) {
-        const int cb = h_inst_clause_begin[b], ce = h_inst_clause_begin[b + 1];
-        const int64_t lb = h_clause_lit_begin[cb], le = h_clause_lit_begin[ce];
-        uint32_t mv = 0;
-        for (int64_t j = lb; j < le; ++j) mv = std::max(mv, (uint32_t)std::abs(h_lits[j]));
-        int d;
-        if (mv <= 63) {   // the common case: the variable set is one word
-            uint64_t used = 0;
-            for (int64_t j = lb; j < le; ++j) used |= 1ull << std::abs(h_lits[j]);
-            d = __builtin_popcountll(used);
-            if (d <= 31)
-                for (int c = cb; c < ce; ++c) {
-                    uint64_t k = 0;
-                    for (int64_t j = h_clause_lit_begin[c]; j < h_clause_lit_begin[c + 1]; ++j) {
-                        const int x = h_lits[j], v = std::abs(x);
-                        const int idx = __builtin_popcountll(used & ((1ull << v) - 1ull));
-                        k |= 1ull << (idx + (x < 0 ? 32 : 0));
-                    }
-                    keys[(size_t)c] = k;
-                }
-            if (record && d <= 31)
-                for (int v = 1; v <= 63; ++v)
-                    if ((used >> v) & 1ull) d2v.push_back(v);
-        } else {
-            vars.clear();
-            for (int64_t j = lb; j < le; ++j) vars.push_back(std::abs(h_lits[j]));
-            std::sort(vars.begin(), vars.end());
-            vars.erase(std::unique(vars.begin(), vars.end()), vars.end());
-            d = (int)std::min<size_t>(vars.size(), 1 << 20);
-            if (d <= 31)
-                for (int c = cb; c < ce; ++c) {
-                    uint64_t k = 0;
-                    for (int64_t j = h_clause_lit_begin[c]; j < h_clause_lit_begin[c + 1]; ++j) {
-                        const int x = h_lits[j];
-                        const int idx = (int)(std::lower_bound(vars.begin(), vars.end(), std::abs(x)) - vars.begin());
-                        k |= 1ull << (idx + (x < 0 ? 32 : 0));
-                    }
-                    keys[(size_t)c] = k;
-                }
-            if (record && d <= 31) d2v.insert(d2v.end(), vars.begin(), vars.end());
-        }
-        nv[(size_t)b] = d;
-        d2v_off[(size_t)b + 1] = (int64_t)d2v.size();
-        if (d <= 31) {
-            int64_t p3 = 1;
-            for (int k = 0; k < d && p3 <= RB_KEY_CAP_MAX; ++k) p3 *= 3;
-            need = std::max<int64_t>(need, p3 + (ce - cb));
-        }
+        const int d = K.nvars[(size_t)b];
+        if (d > BATCH_MAXVARS) continue;
+        int64_t p3 = 1;
+        for (int k = 0; k < d && p3 <= RB_KEY_CAP_MAX; ++k) p3 *= 3;
+        need = std::max<int64_t>(need, p3 + (h_inst_clause_begin[b + 1] - h_inst_clause_begin[b]));
     }
     Tier tier = RB_TIERS[RB_NTIERS - 1];
     for (int t = RB_NTIERS - 1; t >= 0; --t)
@@ -408,7 +316,7 @@ extern "C" int satmi_resolution_batch_host(int num_instances, const int32_t *h_i
     // passes that add clauses <= keys: the device keeps min(pass_cap, key_cap) counts per formula
     const int PC = std::min(pass_cap, tier.key_cap);
 
-    // ---- the workspace
+    // ---- lease the workspace
     int dev = 0;
     DeviceFacts facts;
     SATMI_TRY(device_facts(&facts, &dev));
@@ -417,30 +325,32 @@ extern "C" int satmi_resolution_batch_host(int num_instances, const int32_t *h_i
         set_error("satmi_resolution_batch_host: hipStreamCreate failed");
         return SATMI_ERR_HIP;
     }
-    lease.ok = true;   // whatever the call's outcome (see ResBatchWork)
+    lease.ok = true;   // whatever the call's outcome (see BatchWork)
     ResBatchWork &wk = *lease.w;
     hipStream_t s = wk.stream;
-    const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // inputs, one copy: clause ranges, variable counts, keys
-    const size_t u_nv = al(4 * (size_t)(B + 1)), u_keys = u_nv + al(4 * (size_t)B);
-    const size_t up_bytes = u_keys + al(8 * (size_t)std::max(C, 1));
-    // outputs, zeroed, one copy back: work words, results, passes, key offsets, per-pass counts
-    const size_t o_res = 256, o_pas = o_res + al(4 * (size_t)B), o_off = o_pas + al(4 * (size_t)B);
-    const size_t o_pn = o_off + al(8 * (size_t)B), out_bytes = o_pn + al(8 * (size_t)B * (size_t)std::max(PC, 1));
+    // ---- carve.  Inputs, one copy: clause ranges, variable counts, keys
+    Carve cu;
+    const size_t u_icb = cu.take(4 * (size_t)(B + 1)), u_nv = cu.take(4 * (size_t)B);
+    const size_t u_keys = cu.take(8 * K.keys.size()), up_bytes = cu.at;
+    // outputs, zeroed, one copy back: work word (0) and key cursor (8), results, passes, key offsets, per-pass counts
+    Carve co;
+    const size_t o_work = co.take(16), o_res = co.take(4 * (size_t)B), o_pas = co.take(4 * (size_t)B);
+    const size_t o_off = co.take(8 * (size_t)B), o_pn = co.take(8 * (size_t)B * (size_t)std::max(PC, 1));
+    const size_t out_bytes = co.at;
     SATMI_TRY(wk.up.reserve(up_bytes, &RB_OOM));
     SATMI_TRY(wk.out.reserve(out_bytes, &RB_OOM));
-    SATMI_TRY(wk.up_h.reserve(up_bytes));
-    SATMI_TRY(wk.out_h.reserve(out_bytes));
+    SATMI_TRY(wk.up_h.grow(up_bytes));
+    SATMI_TRY(wk.out_h.grow(out_bytes));
     if (record) SATMI_TRY(wk.keys_out.reserve(8 * (size_t)B * (size_t)tier.key_cap, &RB_OOM));
-    std::memcpy(wk.up_h.p, h_inst_clause_begin, 4 * (size_t)(B + 1));
-    std::memcpy(wk.up_h.p + u_nv, nv.data(), 4 * (size_t)B);
-    std::memcpy(wk.up_h.p + u_keys, keys.data(), 8 * (size_t)std::max(C, 1));
+    std::memcpy(wk.up_h.p + u_icb, h_inst_clause_begin, 4 * (size_t)(B + 1));
+    std::memcpy(wk.up_h.p + u_nv, K.nvars.data(), 4 * (size_t)B);
+    std::memcpy(wk.up_h.p + u_keys, K.keys.data(), 8 * K.keys.size());
     SATMI_HIP(hipMemcpyAsync(wk.up.p, wk.up_h.p, up_bytes, hipMemcpyHostToDevice, s));
     SATMI_HIP(hipMemsetAsync(wk.out.p, 0, out_bytes, s));
 
     unsigned char *up = wk.up.as<unsigned char>(), *out = wk.out.as<unsigned char>();
     ResBatchArgs A;
-    A.icb = (const int32_t *)up;
+    A.icb = (const int32_t *)(up + u_icb);
     A.nvars = (const int32_t *)(up + u_nv);
     A.keys_in = (const uint64_t *)(up + u_keys);
     A.num_instances = B;
@@ -454,23 +364,19 @@ extern "C" int satmi_resolution_batch_host(int num_instances, const int32_t *h_i
     A.pass_cap = PC;
     A.keys_out = record ? wk.keys_out.as<uint64_t>() : nullptr;
     A.key_off = (unsigned long long *)(out + o_off);
-    A.cursor = (unsigned long long *)(out + 8);
-    A.work = (uint32_t *)out;
-    // a persistent grid: the workgroups a CU holds by LDS and by its 32 wave slots
+    A.cursor = (unsigned long long *)(out + o_work + 8);
+    A.work = (uint32_t *)(out + o_work);
+
+    // ---- launch: one persistent grid
     if (B <= facts.cus) tier.threads = tier.threads_few;
-    const int waves = tier.threads / 64;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>({RB_LDS_PER_CU / (lds_bytes + 64), (size_t)(32 / waves), 16}));
-    int grid = (int)std::min<int64_t>(B, (int64_t)facts.cus * per_cu);
-    if (dbg_grid > 0) grid = std::min(grid, dbg_grid);
-    if (lds_bytes > 48 * 1024)
-        SATMI_HIP(hipFuncSetAttribute((const void *)res_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lds_bytes));
+    const int grid = batch_grid(facts, lds_bytes, RB_LDS_SLACK, tier.threads, B, dbg_grid);
+    SATMI_TRY(batch_allow_lds((const void *)res_batch_kernel, lds_bytes));
     hipLaunchKernelGGL(res_batch_kernel, dim3(grid), dim3(tier.threads), lds_bytes, s, A);
     SATMI_HIP(hipGetLastError());
     SATMI_HIP(hipMemcpyAsync(wk.out_h.p, wk.out.p, out_bytes, hipMemcpyDeviceToHost, s));
     SATMI_HIP(hipStreamSynchronize(s));
 
-    // ---- results
+    // ---- copy back
     const unsigned char *oh = wk.out_h.p;
     const int32_t *r_res = (const int32_t *)(oh + o_res), *r_pas = (const int32_t *)(oh + o_pas);
     const unsigned long long *r_off = (const unsigned long long *)(oh + o_off);
@@ -488,16 +394,15 @@ extern "C" int satmi_resolution_batch_host(int num_instances, const int32_t *h_i
     }
     if (!record) return SATMI_OK;
 
-    // ---- the record: each formula's passes decoded from its keys, formula
+    // ---- decode the record: each formula's passes from its keys, formula
     // after formula, in satmi_resolution_host's format and with its truncation
-    const unsigned long long nkeys = *(const unsigned long long *)(oh + 8);
+    const unsigned long long nkeys = *(const unsigned long long *)(oh + o_work + 8);
     std::vector<uint64_t> hk((size_t)nkeys);
     if (nkeys) {
         SATMI_HIP(hipMemcpyAsync(hk.data(), wk.keys_out.p, 8 * (size_t)nkeys, hipMemcpyDeviceToHost, s));
         SATMI_HIP(hipStreamSynchronize(s));
     }
-    // (B x key_cap keys of room: not kept in the pool past a large recorded batch)
-    if (wk.keys_out.cap > ((size_t)64 << 20)) wk.keys_out.release();
+    wk.drop_large_record();   // (B x key_cap keys of room)
     int64_t rec_clauses = 0, rec_lits = 0;
     if (rec_clause_cap > 0) h_rec_clause_off[0] = 0;
     std::vector<std::vector<int32_t>> pass;
@@ -505,19 +410,18 @@ extern "C" int satmi_resolution_batch_host(int num_instances, const int32_t *h_i
         int64_t *prow = h_rec_pass_off + (size_t)b * ((size_t)pass_cap + 1);
         prow[0] = rec_clauses;
         const int np = r_res[b] == SATMI_RES_BATCH_UNFIT ? 0 : std::min(r_pas[b], PC);
-        const int32_t *dv = d2v.data() + d2v_off[(size_t)b];
-        const int V = (int)(d2v_off[(size_t)b + 1] - d2v_off[(size_t)b]);
+        const int32_t *dv = K.d2v.data() + (size_t)b * BATCH_D2V_STRIDE;
+        const int V = std::min(K.nvars[(size_t)b], BATCH_D2V_STRIDE);
         const uint64_t *k = hk.data() + (np > 0 ? r_off[b] : 0ull);
         for (int p = 0; p < np; ++p) {
             const int64_t nnew = r_pn[(size_t)b * (size_t)PC + p];
             // each clause as ascending literals, the clauses in ascending order
-            pass.assign((size_t)nnew, {});
+            pass.resize((size_t)nnew);
             for (int64_t c = 0; c < nnew; ++c) {
-                for (int d = 0; d < V; ++d) {
-                    if ((k[c] >> d) & 1ull) pass[(size_t)c].push_back(dv[d]);
-                    if ((k[c] >> (32 + d)) & 1ull) pass[(size_t)c].push_back(-dv[d]);
-                }
-                std::sort(pass[(size_t)c].begin(), pass[(size_t)c].end());
+                int32_t cl[64];
+                const int n = batch_decode(k[c], dv, V, cl);
+                std::sort(cl, cl + n);
+                pass[(size_t)c].assign(cl, cl + n);
             }
             k += nnew;
             std::sort(pass.begin(), pass.end());

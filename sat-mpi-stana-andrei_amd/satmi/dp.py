@@ -10,8 +10,8 @@ import ctypes
 
 import numpy as np
 
-from . import _capi
-from .resolution import _csr, _p
+from . import _batch, _capi
+from ._batch import _csr, _p
 
 
 class DavisPutnamLimit(Exception):
@@ -138,25 +138,18 @@ def eliminate_batch(formulas, step_limit=0, clause_limit=0, time_limit=0.0, reco
           list order, every clause's literals ascending by variable id (+v
           before -v) -- not eliminate()'s set iteration order; "single"
           results are normalised to the same order."""
-    from . import cnf
     L = _capi.load()
-    if isinstance(formulas, cnf.CnfBatch):
-        cb = formulas
-    else:
-        formulas = list(formulas)
-        cb = cnf.pack(formulas) if formulas else None
-    if cb is None or cb.num_instances == 0:
+    inp = _batch.packed(formulas)
+    if inp is None:
         return []
-    _capi.require_gpu()
+    cb, arrays = inp
     B = cb.num_instances
     res = np.zeros(B, dtype=np.int32)
     steps = np.zeros(B, dtype=np.int32)
     trace = np.zeros((B, _STEP_CAP), dtype=np.int32)
     sc = np.zeros((B, _STEP_CAP), dtype=np.int64)
-    icb, clb, lits = (np.ascontiguousarray(a, dtype=np.int32)
-                      for a in (cb.inst_clause_begin, cb.clause_lit_begin, cb.lits))
     i64 = ctypes.c_int64
-    args = (B, _p(icb), _p(clb), _p(lits), int(step_limit), int(clause_limit), _p(res), _p(steps), _p(trace),
+    args = (B, *map(_p, arrays), int(step_limit), int(clause_limit), _p(res), _p(steps), _p(trace),
             _p(sc, i64), _STEP_CAP)
     if not record:
         _capi.check(L.satmi_dp_batch_host(*args, None, 0, None, 0, None), "satmi_dp_batch_host")

@@ -5,34 +5,15 @@ plus, optionally, the set of clauses each pass added; `resolution_solve` is the
 reference's boolean entry point.
 """
 import ctypes
-import itertools
 
 import numpy as np
 
-from . import _capi
+from . import _batch, _capi
+from ._batch import _csr, _p
 
 
 class ResolutionLimit(Exception):
     """A pass / clause / time limit stopped the saturation before a verdict."""
-
-
-def _csr(formula):
-    """The formula's CSR host arrays (clause offsets, literals), built without a
-    per-literal Python loop (a call's conversion is part of its time)."""
-    off = np.zeros(len(formula) + 1, dtype=np.int32)
-    np.cumsum(np.fromiter(map(len, formula), dtype=np.int32, count=len(formula)), out=off[1:])
-    n = int(off[-1])
-    if n == 0:
-        return off, np.zeros(1, dtype=np.int32)
-    # (a literal outside int32 raises OverflowError here, like np.asarray did)
-    flat = np.fromiter(itertools.chain.from_iterable(formula), dtype=np.int32, count=n)
-    if not flat.all():
-        raise ValueError("literal 0 is not allowed (REF.py:51)")
-    return off, flat
-
-
-def _p(a, t=ctypes.c_int32):
-    return a.ctypes.data_as(ctypes.POINTER(t))
 
 
 def resolve(formula, max_passes=0, clause_limit=0, time_limit=0.0, record=False, rec_cap=1 << 22):
@@ -79,17 +60,16 @@ def debug_batch(grid=0, key_cap=0):
     _capi.check(_capi.load().satmi_resolution_debug_batch(int(grid), int(key_cap)), "satmi_resolution_debug_batch")
 
 
-def _batch_call(L, cb, max_passes, clause_limit, record, pcap, rec_cap):
+def _batch_call(L, cb, arrays, max_passes, clause_limit, record, pcap, rec_cap):
     """One satmi_resolution_batch_host call -> (result[B], passes[B], pass_new[B, pcap], clauses or None),
     clauses[b][p] = the sorted clauses formula b's pass p added."""
     B = cb.num_instances
     res = np.zeros(B, dtype=np.int32)
     passes = np.zeros(B, dtype=np.int32)
     pass_new = np.zeros((B, pcap), dtype=np.int64)
-    icb, clb, lits = (np.ascontiguousarray(a, dtype=np.int32)
-                      for a in (cb.inst_clause_begin, cb.clause_lit_begin, cb.lits))
-    args = (B, _p(icb), _p(clb), _p(lits), int(max_passes), int(clause_limit),
+    args = (B, *map(_p, arrays), int(max_passes), int(clause_limit),
             _p(res), _p(passes), _p(pass_new, ctypes.c_int64), pcap)
+
     if not record:
         _capi.check(L.satmi_resolution_batch_host(*args, None, 0, None, 0, None), "satmi_resolution_batch_host")
         return res, passes, pass_new, None
@@ -116,48 +96,38 @@ def resolve_batch(formulas, max_passes=0, clause_limit=0, time_limit=0.0, record
     take (more than 31 variables, or more clauses than its capacity), which is
     run through resolve() -- `time_limit` applies to those calls only: the
     batched kernel's work is bounded by its capacity."""
-    from . import cnf
     L = _capi.load()
-    if isinstance(formulas, cnf.CnfBatch):
-        cb = formulas
-    else:
-        formulas = list(formulas)
-        cb = cnf.pack(formulas) if formulas else None
-    if cb is None or cb.num_instances == 0:
+    inp = _batch.packed(formulas)
+    if inp is None:
         return []
-    _capi.require_gpu()
+    cb = inp[0]
     B = cb.num_instances
     pcap = int(max_passes) if 0 < max_passes < _PASS_CAP else _PASS_CAP
-    res, passes, pass_new, clauses = _batch_call(L, cb, max_passes, clause_limit, record, pcap, rec_cap)
-    out = []
-    for b in range(B):
-        if res[b] == _capi.RES_BATCH_UNFIT:
-            r = resolve(cb.instance(b), max_passes=max_passes, clause_limit=clause_limit, time_limit=time_limit,
-                        record=record)
-            r["path"] = "single"
-        else:
-            n = int(passes[b])
-            r = {"result": int(res[b]), "passes": n, "pass_new": pass_new[b, :min(n, pcap)].tolist()}
-            if record:
-                r["clauses"] = clauses[b]
-            r["path"] = "batch"
-        out.append(r)
+
+    out = [None] * B
+
+    def fill(rows, call):   # out[b] for every (b, k) of rows: formula b from row k of a call's outputs
+        res, passes, pass_new, clauses = call
+        for b, k in rows:
+            if res[k] == _capi.RES_BATCH_UNFIT:
+                r = resolve(cb.instance(b), max_passes=max_passes, clause_limit=clause_limit, time_limit=time_limit,
+                            record=record)
+                r["path"] = "single"
+            else:
+                n = int(passes[k])
+                r = {"result": int(res[k]), "passes": n, "pass_new": pass_new[k, :n].tolist()}   # (at most the row)
+                if record:
+                    r["clauses"] = clauses[k]
+                r["path"] = "batch"
+            out[b] = r
+
+    fill(zip(range(B), range(B)), _batch_call(L, *inp, max_passes, clause_limit, record, pcap, rec_cap))
     # formulas with more passes than the first call kept counts for: once more, with room for all
+    # (the same capacity rule, so none of them is expected to come back UNFIT)
     more = [b for b in range(B) if out[b]["path"] == "batch" and out[b]["passes"] > pcap]
     if more:
-        sub = cnf.pack([cb.instance(b) for b in more])
-        res, passes, pass_new, clauses = _batch_call(L, sub, max_passes, clause_limit, record, _PASS_CAP_MAX, rec_cap)
-        for k, b in enumerate(more):
-            if res[k] == _capi.RES_BATCH_UNFIT:   # (the same capacity rule: not expected)
-                out[b] = resolve(cb.instance(b), max_passes=max_passes, clause_limit=clause_limit,
-                                 time_limit=time_limit, record=record)
-                out[b]["path"] = "single"
-                continue
-            n = int(passes[k])
-            out[b] = {"result": int(res[k]), "passes": n, "pass_new": pass_new[k, :n].tolist()}
-            if record:
-                out[b]["clauses"] = clauses[k]
-            out[b]["path"] = "batch"
+        sub = _batch.packed([cb.instance(b) for b in more])
+        fill(zip(more, range(len(more))), _batch_call(L, *sub, max_passes, clause_limit, record, _PASS_CAP_MAX, rec_cap))
     return out
 
 

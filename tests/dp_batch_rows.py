@@ -160,6 +160,13 @@ def mix():
     return fs
 
 
+def sparse_mix():
+    """The first 40 formulas of mix() with v -> v + 64: every id is above 63, so
+    the host encodes them on its sorted path (csrc/batch_keys.h), and the live
+    ids 65 .. 72 still sit at distinct homes in 8 and in 32 slots."""
+    return [[[l + 64 if l > 0 else l - 64 for l in c] for c in f] for f in mix()[:40]]
+
+
 def _triples(k, seed):
     """k distinct 3-literal clauses over the variables 2 .. 9, no two on the same
     literals: none is a subset of another."""

@@ -194,6 +194,19 @@ def test_rows_mix():
         _same_as_oracle(f)
 
 
+def test_rows_sparse_mix():
+    """The renamed rows of test_dp_batch_gpu.py::test_sparse_ids: ids above 63
+    only, and the batched kernel takes every one of them."""
+    fs = R.sparse_mix()
+    assert len(fs) == 40 and all(min(R.variables(f)) > 63 for f in fs)
+    ps = [R.profile(f) for f in fs]
+    assert all(R.fits(p, 512) for p in ps)                       # none is excused
+    assert max(p["max_list"] for p in ps) == 30
+    assert {p["oracle"]["result"] for p in ps} == {0, 1}
+    for f in fs:
+        _same_as_oracle(f)
+
+
 def test_rows_capacity():
     """At SMALL_CAP clauses some rows overflow on input, some in a later list, some never."""
     fs = R.capacity_rows()

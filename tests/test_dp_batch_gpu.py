@@ -73,6 +73,17 @@ def test_random_mix_matches_oracle(mix):
     assert plain == [{k: v for k, v in r.items() if k != "clauses"} for r in got]
 
 
+def test_sparse_ids():
+    """Variable ids above 63 take the host encoder's sorted path: the first 40
+    formulas of the mix renamed v -> v + 64 (tests/test_dp_batch.py proves that
+    the kernel takes every one), exact against the oracle with the record."""
+    fs = R.sparse_mix()
+    got = eliminate_batch(fs, record=True)
+    assert len(got) == 40
+    for f, r in zip(fs, got):
+        _same(r, _want(f), f)                              # every one on the batch path
+
+
 def test_slot_order_and_collisions():
     fs = [R.SLOT, R.SLOT37, R.COLLIDE0, R.COLLIDE1]
     got = eliminate_batch(fs, record=True)

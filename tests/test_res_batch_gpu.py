@@ -95,6 +95,39 @@ def test_workgroup_reuse(mix):
         assert again[k] == got[b], (k, b, fs[b])
 
 
+def _want_limited(f, lim):
+    """The oracle's saturation of f as clause_limit=lim ends it: after the first
+    pass that brings the clause count over lim (the oracle's own clause_limit
+    stops in the middle of that pass, so max_passes is the comparison)."""
+    o = oracle.resolution(f, record=True)
+    over = [p for p, n in enumerate(len(f) + np.cumsum(o["pass_new"])) if n > lim]
+    if not over:
+        return o
+    o = oracle.resolution(f, max_passes=over[0] + 1, record=True)
+    assert o["result"] == -1 and o["passes"] == over[0] + 1
+    return o
+
+
+def test_sparse_ids(mix):
+    """Variable ids above 63 take the host encoder's sorted path: every third of
+    the first 40 formulas renamed v -> 1000 v (both paths in one batch), a
+    formula over {1, 70, INT32_MAX}, a chain of 31 sparse variables (still one
+    key: the batch path, stopped by clause_limit) and one of 32 (handed back)."""
+    fs, _, _ = mix
+    big = 2 ** 31 - 1
+    rows = [[[1000 * l for l in c] for c in f] if b % 3 == 0 else f for b, f in enumerate(fs[:40])]
+    rows.append([[1, -70], [70, big], [-big, -1], [1, 70, big], [-70, -big]])
+    rows.append([[i, -(i + 1)] for i in range(100, 130)])      # ids 100 .. 130: 31 variables
+    rows.append([[i, -(i + 1)] for i in range(100, 131)])      # ids 100 .. 131: 32
+    assert [len({abs(l) for c in f for l in c}) for f in rows[-3:]] == [3, 31, 32]
+    want = [_want_limited(f, 64) for f in rows]
+    assert all(o["result"] in (0, 1) for o in want[:41]) and [o["result"] for o in want[41:]] == [-1, -1]
+    got = resolve_batch(rows, clause_limit=64, record=True)
+    assert [r["path"] for r in got] == ["batch"] * 42 + ["single"]
+    for f, r, o in zip(rows, got, want):
+        _same(r, o, f)
+
+
 def _c_call(formulas, pass_cap, rec_lit_cap=None, rec_clause_cap=None, max_passes=0):
     """satmi_resolution_batch_host with guard words after every output array."""
     L = _capi.load()
