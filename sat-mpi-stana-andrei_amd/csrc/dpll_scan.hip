@@ -52,11 +52,11 @@ namespace {
 #ifdef SATMI_PHASE_STAMPS
 struct PhaseClock {
     uint64_t acc[8];
-    uint64_t cnt[16];   // path counts (written after the clocks)
+    uint64_t cnt[24];   // path counts (written after the clocks)
     uint64_t t;
     __device__ void start() {
         for (int i = 0; i < 8; ++i) acc[i] = 0;
-        for (int i = 0; i < 16; ++i) cnt[i] = 0;
+        for (int i = 0; i < 24; ++i) cnt[i] = 0;
         t = __builtin_amdgcn_s_memtime();
     }
     __device__ void count(int i, uint64_t v = 1) { cnt[i] += v; }
@@ -474,6 +474,13 @@ __device__ int inc_units(const SLds<K, C> &S, int nw, int rs, int tl, uint32_t e
             const int nun = __popcll(um);
             ph.count(4, (uint64_t)nun);
             ph.count(nun == 0 ? 10 : nun == 1 ? 11 : nun == 2 ? 12 : nun <= 8 ? 13 : 6, nun <= 8 ? 1 : 0);
+            // one-step rounds of 3+ units by batch size (1, 2, 3-4, 5+), and the 2-unit rounds of a batch of one
+            if (nun > FAST_UNITS) ph.count(tl - rs == 1 ? 16 : tl - rs == 2 ? 17 : tl - rs <= 4 ? 18 : 19);
+            else if (nun == 2 && tl - rs == 1) ph.count(20);
+            // A batch of one literal touches one occurrence list, which is
+            // ascending (build_occurrences): the valid lanes hold distinct
+            // clauses in clause order, so lane order is snapshot order.
+            const bool one_list = tl - rs == 1;
             if (__builtin_expect(nun <= FAST_UNITS, 1)) {
                 ph.count(3);
                 // a clause reached from two batch literals is one snapshot entry
@@ -486,6 +493,9 @@ __device__ int inc_units(const SLds<K, C> &S, int nw, int rs, int tl, uint32_t e
                 const uint32_t code = unit_code<K>(w, x);
                 bool keep = unit;
                 int nkeep = nun;
+                // (two units of one list need no clause compare either, but a
+                // second form of this block measured 1.6 % slower on the bench:
+                // profiles/lane_order/)
                 if (nun == 2) {   // lanes u0 < u1
                     const int u0 = __builtin_ctzll(um), u1 = 63 - __builtin_clzll(um);
                     const uint32_t c0 = (uint32_t)__builtin_amdgcn_readlane((int)c, u0);
@@ -507,7 +517,32 @@ __device__ int inc_units(const SLds<K, C> &S, int nw, int rs, int tl, uint32_t e
                 *pre = nkeep;
                 return __popcll(dm);
             }
-            // more units than the register ranking takes: the touched clauses
+            // More units than the register ranking takes, from one list: a
+            // unit's snapshot index is the count of unit lanes below it.  The
+            // stamps still pick the first entry of each variable (REF.py:149-152)
+            // and carry the index for the conflict cut; the first entries are
+            // assigned right here in lane order, as above, so there is no
+            // bitmap, no snapshot write and no assignment loop in the next round.
+            if (one_list) {
+                ph.count(21);
+                const uint32_t code = unit_code<K>(w, x);
+                const uint32_t v = unit ? code >> 1 : 0u;   // (variable 0 is never stamped)
+                const uint32_t st = stamp(ep, __builtin_amdgcn_mbcnt_hi((uint32_t)(um >> 32),
+                                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)um, 0u)));
+                if (unit) ts_stamp(S, v, st);
+                wave_sync();
+                const bool first = unit & (ts_first(S, v) == st);
+                const uint64_t fm = __ballot(first);
+                if (first) {
+                    S.trail[__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32),
+                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)fm, (uint32_t)tl))] = (C)code;
+                    lv_assign(S.lv, code);
+                }
+                wave_sync();
+                *pre = __popcll(fm);
+                return nun;
+            }
+            // ... from several lists: the touched clauses
             // are already in the lanes (one step), so they are placed in clause
             // order through the bitmap right here, not scanned again below (a
             // clause reached from two batch literals sets one bit; its lanes
@@ -975,9 +1010,11 @@ __device__ void store_assignment(const SLds<K, C> &S, int tl, int32_t *out) {
 enum { ST_PROPAGATE = 0, ST_ANALYZE = 1, ST_BACKTRACK = 2, ST_DONE = 3 };
 
 // Incremental kernel: occurrence lists of the staged clauses, S.occ[S.occ_off[x] ..
-// S.occ_off[x+1]) = the clauses holding literal code x (each clause once, in no
-// particular order -- the unit bitmap restores clause order).  cnt is borrowed
-// as the per-code counter / fill cursor and left zeroed.
+// S.occ_off[x+1]) = the clauses holding literal code x, each clause once, in
+// strictly ascending clause index -- a unit scan over one list holds its
+// clauses in clause order by lane (inc_units); over several lists the unit
+// bitmap restores clause order.  cnt is borrowed as the per-code counter / fill
+// cursor and left zeroed.
 template <int K, typename C>
 __device__ void build_occurrences(const SLds<K, C> &S, uint16_t *occ, int m, int n) {
     using W = typename Pack<K>::W;
@@ -1022,6 +1059,31 @@ __device__ void build_occurrences(const SLds<K, C> &S, uint16_t *occ, int m, int
     else
         for (int v = ln; v <= n; v += 64) S.cnt[v] = 0u;
     // the lists are read back by this wave only: complete the stores first
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    wave_sync();
+    // The fill files the 64-clause blocks in ascending order, but a block's
+    // entries in the order its atomics ran.  One lane per literal code sorts
+    // its list by insertion: the lists are short (n=100: 6.4 entries on
+    // average) and nearly sorted, so a list costs about one read per entry,
+    // once per instance.
+    for (int x = 2 + ln; x < 2 * (n + 1); x += 64) {
+        const int o0 = S.occ_off[x], o1 = S.occ_off[x + 1];
+        uint32_t last = o0 < o1 ? occ[o0] : 0u;   // the largest of [o0, i), at i - 1
+        for (int i = o0 + 1; i < o1; ++i) {
+            const uint32_t key = occ[i];
+            if (key > last) {
+                last = key;
+                continue;
+            }
+            int j = i;
+            uint32_t prev = last;
+            do {
+                occ[j] = (uint16_t)prev;
+                --j;
+            } while (j > o0 && (prev = occ[j - 1]) > key);
+            occ[j] = (uint16_t)key;
+        }
+    }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     wave_sync();
 }
@@ -1659,7 +1721,8 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
     }
 #ifdef SATMI_PHASE_STAMPS
     ph.mark(PH_OTHER);
-    if (!is_task && A.root_lits && A.sol_stride >= 48 && ln < 24)
+    // 8 clocks and 16 counts in a row of 48 words; a row of 64 takes all 24 counts
+    if (!is_task && A.root_lits && A.sol_stride >= 48 && ln < (A.sol_stride >= 64 ? 32 : 24))
         ((int64_t *)(A.root_lits + (int64_t)b * A.sol_stride))[ln] = (int64_t)(ln < 8 ? ph.acc[ln] : ph.cnt[ln - 8]);
 #endif
     if (SPLIT && status == STATUS_HANDED) return false;   // counters and ticks are in the row already

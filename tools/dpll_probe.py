@@ -84,10 +84,16 @@ def main():
             out["rounds_per_node"] = float(c[:, 6].sum()) / nodes
             if kern in (_capi.KERNEL_SCAN, _capi.KERNEL_INC) and root.shape[1] >= 48:
                 # path counts of the incremental unit scan (csrc/dpll_scan.hip inc_units, diag build)
-                cn = root[:, :48].cpu().contiguous().view(torch.int64)[:, 8:24].double().sum(0)
+                # (a row of 64 words or more carries all 24 counts, a shorter one the first 16)
+                nc = 24 if root.shape[1] >= 64 else 16
+                cn = root[:, :2 * (8 + nc)].cpu().contiguous().view(torch.int64)[:, 8:8 + nc].double().sum(0)
                 cnames = ("unit_scans", "fast_one_step", "fast_conflict", "fast_few_units", "units_found",
                           "general", "fast_bitmap", "batch_literals", "general_batch_gt16", "general_touched_gt64",
-                          "fast_nun0", "fast_nun1", "fast_nun2", "fast_nun3_8", "propagate_calls", "assign_steps")
+                          "fast_nun0", "fast_nun1", "fast_nun2", "fast_nun3_8", "propagate_calls", "assign_steps",
+                          # one-step rounds of 3+ units by batch size, the 2-unit rounds of a batch of one,
+                          # and the 3+-unit rounds ranked by lane order
+                          "many_units_batch1", "many_units_batch2", "many_units_batch3_4", "many_units_batch5up",
+                          "two_units_batch1", "lane_order_rounds")[:nc]
                 out["per_node"] = {nm: float(cn[i]) / nodes for i, nm in enumerate(cnames)}
         print(json.dumps(out), flush=True)
 
