@@ -1,6 +1,7 @@
 // batch_host.h -- the launch-side pieces the two batched entry points
 // (resolution_batch.hip, dp_batch.hip) share: the workspace a call leases, the
-// carving of its blocks, the persistent grid's size, the dynamic-LDS attribute.
+// persistent grid's size, the dynamic-LDS attribute (its blocks are carved with
+// host.h's Carve).
 // The launch sequences differ (Davis-Putnam launches twice when it records).
 #pragma once
 #include "batch_keys.h"
@@ -26,25 +27,13 @@ struct BatchWork {
     }
 };
 
-// Offsets of the arrays of one block, each 256-byte aligned; `at` ends as its size.
-struct Carve {
-    size_t at = 0;
-    size_t take(size_t bytes) {
-        const size_t off = at;
-        at += (bytes + 255) & ~(size_t)255;
-        return off;
-    }
-};
-
-constexpr size_t BATCH_LDS_PER_CU = 160 * 1024;
-
 // Workgroups of a persistent grid over B formulas: as many as the CUs hold --
 // by LDS (`lds_bytes` dynamic and `lds_slack` static per workgroup), by a CU's
 // 32 wave slots, and 16 at the most -- capped by the test knob `dbg_grid` (0 = none).
 inline int batch_grid(const DeviceFacts &facts, size_t lds_bytes, size_t lds_slack, int threads, int B, int dbg_grid) {
     const int waves = threads / 64;
     const int per_cu =
-        (int)std::max<size_t>(1, std::min<size_t>({BATCH_LDS_PER_CU / (lds_bytes + lds_slack), (size_t)(32 / waves), 16}));
+        (int)std::max<size_t>(1, std::min<size_t>({LDS_PER_CU / (lds_bytes + lds_slack), (size_t)(32 / waves), 16}));
     const int grid = (int)std::min<int64_t>(B, (int64_t)facts.cus * per_cu);
     return dbg_grid > 0 ? std::min(grid, dbg_grid) : grid;
 }

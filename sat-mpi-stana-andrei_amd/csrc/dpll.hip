@@ -72,6 +72,9 @@ struct Narrow {
     static constexpr uint32_t PHASE = 0x8000u;   // fvar: the False branch runs
     static constexpr int NT_SHIFT = 8, SUM_SHIFT = 16, CNT_SHIFT = 16;
     static constexpr int MAX_LEN = 255;
+    // 16-bit literal codes, clause indices, literal positions and per-clause counts
+    static constexpr int MAX_VARS = 32766, MAX_CLAUSES = 65534, MAX_LITS = 65535;
+    static constexpr bool IN_LDS = true;
 };
 struct Wide {
     using Idx = uint32_t;
@@ -80,6 +83,8 @@ struct Wide {
     static constexpr uint32_t PHASE = 0x80000000u;
     static constexpr int NT_SHIFT = 16, SUM_SHIFT = 32, CNT_SHIFT = 32;
     static constexpr int MAX_LEN = 65535;
+    static constexpr int MAX_VARS = (1 << 30) - 2, MAX_CLAUSES = 1 << 28, MAX_LITS = 1 << 30;
+    static constexpr bool IN_LDS = false;
 };
 template <typename T> __device__ __forceinline__ typename T::Cst cst_true1() { return (typename T::Cst)1 << T::NT_SHIFT; }
 template <typename T> __device__ __forceinline__ uint32_t cst_nfree(typename T::Cst s) {
@@ -917,95 +922,81 @@ __global__ void __launch_bounds__(64) dpll_wide_kernel(DpllArgs A, unsigned char
 }
 
 // ------------------------------------------------------------------ host side
-static uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
-
+// The image of an instance in T's storage form: the arrays of LdsT<T> in its
+// order, elements as wide as T's types.  Narrow: one wave's LDS slice, false
+// past a CU's LDS.  Wide: one wave's HBM arena (mark unused: an LDS row),
+// rounded up to 256 B, false when an offset would pass 4 GiB.
+template <typename T>
 static bool make_layout(int max_vars, int max_clauses, int max_lits, DpllLayout *lay) {
     if (max_vars < 0 || max_clauses < 0 || max_lits < 0) return false;
-    // 16-bit literal codes, clause indices, literal positions and per-clause counts
-    if (max_vars > 32766 || max_clauses > 65534 || max_lits > 65535) return false;
-    const uint32_t N = (uint32_t)max_vars + 1, M = (uint32_t)max_clauses + 1, Lc = (uint32_t)max_lits + 1;
-    uint32_t o = 0;
-    lay->lit = o;     o = align16(o + 2 * (Lc + 4));   // +4: clause_counts reads in groups of four
-    lay->coff = o;    o = align16(o + 2 * M);
-    lay->occoff = o;  o = align16(o + 2 * (2 * N + 1));
-    lay->occ = o;     o = align16(o + 2 * Lc);
-    lay->cst = o;     o = align16(o + 4 * M);
-    lay->vst = o;     o = align16(o + 4 * N);
-    lay->cnt = o;     o = align16(o + 4 * N);
-    lay->claim = o;   o = align16(o + 4 * N);
-    lay->trail = o;   o = align16(o + 2 * N);
-    lay->fvar = o;    o = align16(o + 2 * N);
-    lay->ftrail = o;  o = align16(o + 2 * N);
-    lay->units = o;   o = align16(o + 2 * M);
-    lay->ubits = o;   o = align16(o + 8 * ((M + 63) / 64));
-    lay->posbits = o; o = align16(o + 8 * ((Lc + 63) / 64));
-    lay->mark = o;    o = align16(o + 4 * 64);
-    lay->bytes = o;
-    lay->lcap = max_lits;
-    lay->mcap = max_clauses;
-    lay->ncap = max_vars;
-    return o <= 160u * 1024u;
-}
-
-// Wide storage (HBM arena per wave): 32-bit codes / indices / positions, 64-bit
-// clause and count words.  False when an offset would pass 4 GiB.
-static bool make_wide_layout(int max_vars, int max_clauses, int max_lits, DpllLayout *lay) {
-    if (max_vars < 0 || max_clauses < 0 || max_lits < 0) return false;
-    if (max_vars > (1 << 30) - 2 || max_clauses > (1 << 28) || max_lits > (1 << 30)) return false;
+    if (max_vars > T::MAX_VARS || max_clauses > T::MAX_CLAUSES || max_lits > T::MAX_LITS) return false;
     const uint64_t N = (uint64_t)max_vars + 1, M = (uint64_t)max_clauses + 1, Lc = (uint64_t)max_lits + 1;
-    auto a16 = [](uint64_t x) { return (x + 15u) & ~(uint64_t)15u; };
+    constexpr uint64_t IDX = sizeof(typename T::Idx), CST = sizeof(typename T::Cst), CNT = sizeof(typename T::Cnt);
     uint64_t o = 0;
-    uint64_t off[15];
-    off[0] = o;  o = a16(o + 4 * (Lc + 4));        // lit (+4: clause_counts reads in groups of four)
-    off[1] = o;  o = a16(o + 4 * M);               // coff
-    off[2] = o;  o = a16(o + 4 * (2 * N + 1));     // occoff
-    off[3] = o;  o = a16(o + 4 * Lc);              // occ
-    off[4] = o;  o = a16(o + 8 * M);               // cst
-    off[5] = o;  o = a16(o + 4 * N);               // vst
-    off[6] = o;  o = a16(o + 8 * N);               // cnt
-    off[7] = o;  o = a16(o + 8 * N);               // claim
-    off[8] = o;  o = a16(o + 4 * N);               // trail
-    off[9] = o;  o = a16(o + 4 * N);               // fvar
-    off[10] = o; o = a16(o + 4 * N);               // ftrail
-    off[11] = o; o = a16(o + 4 * M);               // units
-    off[12] = o; o = a16(o + 8 * ((M + 63) / 64)); // ubits
-    off[13] = o; o = a16(o + 8 * ((Lc + 63) / 64));// posbits
-    off[14] = o; o = a16(o + 4 * 64);              // mark (unused: LDS row)
-    o = (o + 255u) & ~(uint64_t)255u;              // arenas start on 256-B boundaries
-    if (o >= (1ull << 32)) return false;
-    lay->lit = (uint32_t)off[0];
-    lay->coff = (uint32_t)off[1];
-    lay->occoff = (uint32_t)off[2];
-    lay->occ = (uint32_t)off[3];
-    lay->cst = (uint32_t)off[4];
-    lay->vst = (uint32_t)off[5];
-    lay->cnt = (uint32_t)off[6];
-    lay->claim = (uint32_t)off[7];
-    lay->trail = (uint32_t)off[8];
-    lay->fvar = (uint32_t)off[9];
-    lay->ftrail = (uint32_t)off[10];
-    lay->units = (uint32_t)off[11];
-    lay->ubits = (uint32_t)off[12];
-    lay->posbits = (uint32_t)off[13];
-    lay->mark = (uint32_t)off[14];
+    auto take = [&o](uint64_t bytes) {
+        const uint64_t at = o;
+        o = align16(o + bytes);
+        return (uint32_t)at;   // the last check bounds every offset
+    };
+    lay->lit = take(IDX * (Lc + 4));   // +4: clause_counts reads in groups of four
+    lay->coff = take(IDX * M);
+    lay->occoff = take(IDX * (2 * N + 1));
+    lay->occ = take(IDX * Lc);
+    lay->cst = take(CST * M);
+    lay->vst = take(4 * N);
+    lay->cnt = take(CNT * N);
+    lay->claim = take(CNT * N);
+    lay->trail = take(IDX * N);
+    lay->fvar = take(IDX * N);
+    lay->ftrail = take(IDX * N);
+    lay->units = take(IDX * M);
+    lay->ubits = take(8 * ((M + 63) / 64));
+    lay->posbits = take(8 * ((Lc + 63) / 64));
+    lay->mark = take(4 * 64);
+    if (!T::IN_LDS) o = (o + 255u) & ~(uint64_t)255u;   // arenas start on 256-B boundaries
     lay->bytes = (uint32_t)o;
     lay->lcap = max_lits;
     lay->mcap = max_clauses;
     lay->ncap = max_vars;
-    return true;
+    return T::IN_LDS ? o <= LDS_PER_CU : o < (1ull << 32);
 }
 
-// Which storage form the general kernel takes: the wide form when it is pinned,
-// when the sizes pass the LDS layout (*lay is filled otherwise), and when a
-// clause is longer than the LDS form's clause word counts (Narrow::MAX_LEN) --
-// unless the LDS form is pinned, whose kernel then answers
-// SATMI_DPLL_TOO_LARGE for the instances that hold such a clause.
-// max_clause_len = 0 (unknown) plans by the sizes alone.
-static bool takes_wide(int policy, int max_vars, int max_clauses, int max_lits, int max_clause_len,
-                       DpllLayout *lay) {
-    if (policy == SATMI_KERNEL_WIDE) return true;
-    if (policy != SATMI_KERNEL_GENERAL && max_clause_len > Narrow::MAX_LEN) return true;
-    return !make_layout(max_vars, max_clauses, max_lits, lay);
+// The kernel a batch takes, decided once for satmi_dpll_plan and
+// satmi_dpll_batch_device.  SOUND mode without a caller assignment: a clause
+// kernel (dpll_scan.hip; `inc`: incremental propagation, all but the SCAN
+// policy) when the shape fits it, unless the policy pins the general kernel.
+// Else the general kernel, whose storage form is the wide one when it is
+// pinned, when the sizes pass the LDS layout, and when a clause is longer than
+// the LDS form's clause word counts (Narrow::MAX_LEN) -- unless the LDS form is
+// pinned, whose kernel then answers SATMI_DPLL_TOO_LARGE for the instances
+// that hold such a clause.  max_clause_len = 0 (unknown) plans by the sizes
+// alone.  A SCAN / INC policy that the batch does not fit shows as a `kind`
+// that is not the policy's: only a launch objects.
+struct KernelChoice {
+    int kind = SATMI_KERNEL_GENERAL;   // SATMI_KERNEL_GENERAL / WIDE / SCAN / INC
+    bool inc = false;
+    uint32_t scan_lds = 0;             // SCAN, INC: LDS bytes per wave of the eligibility layout
+    DpllLayout lay{};                  // GENERAL, WIDE
+    int rc = SATMI_OK;                 // SATMI_ERR_TOO_LARGE: past the wide layout too
+    bool scan() const { return kind == SATMI_KERNEL_SCAN || kind == SATMI_KERNEL_INC; }
+};
+static KernelChoice choose_kernel(int policy, int mode, bool has_init, int max_vars, int max_clauses, int max_lits,
+                                  int max_clause_len) {
+    KernelChoice ch;
+    ch.inc = policy != SATMI_KERNEL_SCAN;
+    if (mode == SATMI_MODE_SOUND && !has_init && policy != SATMI_KERNEL_GENERAL &&
+        dpll_scan_eligible(max_vars, max_clauses, max_lits, max_clause_len, ch.inc, &ch.scan_lds)) {
+        ch.kind = ch.inc ? SATMI_KERNEL_INC : SATMI_KERNEL_SCAN;
+        return ch;
+    }
+    const bool wide = policy == SATMI_KERNEL_WIDE ||
+                      (policy != SATMI_KERNEL_GENERAL && max_clause_len > Narrow::MAX_LEN) ||
+                      !make_layout<Narrow>(max_vars, max_clauses, max_lits, &ch.lay);
+    if (wide) {
+        ch.kind = SATMI_KERNEL_WIDE;
+        if (!make_layout<Wide>(max_vars, max_clauses, max_lits, &ch.lay)) ch.rc = SATMI_ERR_TOO_LARGE;
+    }
+    return ch;
 }
 
 // The launch state of every (device, stream) that ran a DPLL batch (DpllStream,
@@ -1047,7 +1038,7 @@ struct NarrowShape {
 static NarrowShape narrow_shape(uint32_t lds_bytes_per_wave) {
     NarrowShape S;
     for (int wpg : {4, 2, 1}) {
-        const int wgs = std::min(16, (int)((160u * 1024u) / (lds_bytes_per_wave * (uint32_t)wpg)));
+        const int wgs = std::min(16, (int)(LDS_PER_CU / (lds_bytes_per_wave * (uint32_t)wpg)));
         const int waves = std::min(32, wgs * wpg);
         if (wgs >= 1 && waves > S.waves_per_cu) {
             S.waves_per_cu = waves;
@@ -1164,30 +1155,22 @@ extern "C" int satmi_dpll_plan(int max_vars, int max_clauses, int max_lits, int 
         set_error("satmi_dpll_plan: null output");
         return SATMI_ERR_ARG;
     }
-    const int policy = g_kernel_policy.load();
-    uint32_t sb = 0;
-    const bool inc = policy != SATMI_KERNEL_SCAN;
-    if (mode == SATMI_MODE_SOUND && !has_init && policy != SATMI_KERNEL_GENERAL &&
-        dpll_scan_eligible(max_vars, max_clauses, max_lits, max_clause_len, inc, &sb)) {
-        *kernel = inc ? SATMI_KERNEL_INC : SATMI_KERNEL_SCAN;
-        const int rc = dpll_scan_resident(max_vars, max_clauses, max_clause_len, inc, waves_per_cu, &sb);
+    const KernelChoice ch = choose_kernel(g_kernel_policy.load(), mode, has_init != 0, max_vars, max_clauses,
+                                          max_lits, max_clause_len);
+    if (ch.rc) {
+        set_error("satmi_dpll_plan: instance too large for the wide (HBM arena) layout");
+        return ch.rc;
+    }
+    *kernel = ch.kind;
+    if (ch.scan()) {
+        uint32_t sb = ch.scan_lds;   // what a failed residency query leaves
+        const int rc = dpll_scan_resident(max_vars, max_clauses, max_clause_len, ch.inc, waves_per_cu, &sb);
         *lds_bytes_per_wave = sb;
         return rc;
     }
-    DpllLayout lay;
-    if (takes_wide(policy, max_vars, max_clauses, max_lits, max_clause_len, &lay)) {
-        if (!make_wide_layout(max_vars, max_clauses, max_lits, &lay)) {
-            set_error("satmi_dpll_plan: instance too large for the wide (HBM arena) layout");
-            return SATMI_ERR_TOO_LARGE;
-        }
-        *kernel = SATMI_KERNEL_WIDE;
-        *lds_bytes_per_wave = 256;   // the arena is in HBM; LDS holds one scratch row
-        *waves_per_cu = 32;
-        return SATMI_OK;
-    }
-    *kernel = SATMI_KERNEL_GENERAL;
-    *lds_bytes_per_wave = lay.bytes;
-    *waves_per_cu = narrow_shape(lay.bytes).waves_per_cu;
+    const bool wide = ch.kind == SATMI_KERNEL_WIDE;
+    *lds_bytes_per_wave = wide ? 256 : ch.lay.bytes;   // wide: the arena is in HBM; LDS holds one scratch row
+    *waves_per_cu = wide ? 32 : narrow_shape(ch.lay.bytes).waves_per_cu;
     return SATMI_OK;
 }
 
@@ -1206,7 +1189,7 @@ extern "C" int satmi_dpll_scan_shape(int max_vars, int max_clauses, int max_clau
 
 extern "C" uint64_t satmi_dpll_lds_bytes(int max_vars, int max_clauses, int max_lits) {
     DpllLayout lay;
-    if (!make_layout(max_vars, max_clauses, max_lits, &lay)) return 0;
+    if (!make_layout<Narrow>(max_vars, max_clauses, max_lits, &lay)) return 0;
     return lay.bytes;
 }
 
@@ -1237,57 +1220,42 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
         return SATMI_ERR_ARG;
     }
     if (num_instances == 0) return SATMI_OK;
-    // SOUND mode without a caller assignment: the clause-scan kernel
-    // (dpll_scan.hip) when the batch shape fits it, unless policy says otherwise
     const int policy = g_kernel_policy.load();
-    const bool inc = policy != SATMI_KERNEL_SCAN;
-    const bool scan_ok = mode == SATMI_MODE_SOUND && !d_init_begin && policy != SATMI_KERNEL_GENERAL &&
-                         dpll_scan_eligible(max_vars, max_clauses, max_lits, max_clause_len, inc, nullptr);
-    if ((policy == SATMI_KERNEL_SCAN || policy == SATMI_KERNEL_INC) && !scan_ok) {
+    const KernelChoice ch = choose_kernel(policy, mode, d_init_begin != nullptr, max_vars, max_clauses, max_lits,
+                                          max_clause_len);
+    if ((policy == SATMI_KERNEL_SCAN || policy == SATMI_KERNEL_INC) && !ch.scan()) {
         set_error("satmi_dpll_batch_device: SATMI_KERNEL_SCAN/INC policy but the batch is not eligible (SOUND "
                   "mode, no caller assignment, clause lengths 1..5, <= 2047 variables)");
         return SATMI_ERR_ARG;
     }
-    DpllLayout lay;
-    const bool wide = !scan_ok && takes_wide(policy, max_vars, max_clauses, max_lits, max_clause_len, &lay);
-    if (wide && !make_wide_layout(max_vars, max_clauses, max_lits, &lay)) {
+    if (ch.rc) {
         set_error("satmi_dpll_batch_device: instance too large (wide layout: vars < 2^30, clauses <= 2^28, "
                   "literals <= 2^30, < 4 GiB per wave)");
-        return SATMI_ERR_TOO_LARGE;
+        return ch.rc;
     }
+    const DpllLayout &lay = ch.lay;
     hipStream_t s = (hipStream_t)stream;
     DpllStream *st = nullptr;
     SATMI_TRY(dpll_stream(s, true, &st));
     DeviceFacts dev;
     SATMI_TRY(device_facts(&dev));
     const uint64_t time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * dev.ticks_per_s) : 0;
+    const DpllBatch batch{d_inst_clause_begin, d_clause_lit_begin, d_lits, d_inst_nvars,   // (DpllBatch's order)
+                          num_instances, sol_cap, sol_stride,
+                          max_solutions, node_limit, time_limit_ticks,
+                          d_status, d_counters, d_sol_len, d_sol_lits, d_root_len, d_root_lits};
     st->split_last = false;   // until the launch takes splitting scratch, it has no split statistics
     SATMI_HIP(hipMemsetAsync(st->counter, 0, 24, s));   // counter + launch span (common.h)
-    if (scan_ok) {
+    if (ch.scan()) {
         ScanLaunch Lc;
-        Lc.num_instances = num_instances;
-        Lc.inst_clause_begin = d_inst_clause_begin;
-        Lc.clause_lit_begin = d_clause_lit_begin;
-        Lc.lits = d_lits;
-        Lc.inst_nvars = d_inst_nvars;
+        Lc.batch = batch;
         Lc.max_vars = max_vars;
         Lc.max_clauses = max_clauses;
         Lc.max_lits = max_lits;
         Lc.max_clause_len = max_clause_len;
-        Lc.max_solutions = max_solutions;
-        Lc.node_limit = node_limit;
-        Lc.time_limit_ticks = time_limit_ticks;
-        Lc.sol_cap = sol_cap;
-        Lc.sol_stride = sol_stride;
-        Lc.status = d_status;
-        Lc.counters = d_counters;
-        Lc.sol_len = d_sol_len;
-        Lc.sol_lits = d_sol_lits;
-        Lc.root_len = d_root_len;
-        Lc.root_lits = d_root_lits;
         Lc.num_cus = dev.cus;
         Lc.st = st;
-        Lc.inc = inc;
+        Lc.inc = ch.inc;
         // branch splitting reproduces the sequential search exactly only when
         // the search stops at its first model and nothing else cuts it short
         const int sm = g_split_enable.load();
@@ -1297,28 +1265,14 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
         Lc.split_warmup = g_split_warmup.load();
         return dpll_scan_launch(Lc);
     }
-    DpllArgs A;
-    A.inst_clause_begin = d_inst_clause_begin;
-    A.clause_lit_begin = d_clause_lit_begin;
-    A.lits = d_lits;
-    A.inst_nvars = d_inst_nvars;
+    DpllArgs A{};
+    bind_batch(A, batch);
     A.init_begin = d_init_begin;
     A.init_lits = d_init_lits;
-    A.num_instances = num_instances;
     A.mode = mode;
-    A.sol_cap = sol_cap;
-    A.sol_stride = sol_stride;
-    A.max_solutions = max_solutions;
-    A.node_limit = node_limit;
-    A.time_limit_ticks = time_limit_ticks;
-    A.status = d_status;
-    A.counters = d_counters;
-    A.sol_len = d_sol_len;
-    A.sol_lits = d_sol_lits;
-    A.root_len = d_root_len;
-    A.root_lits = d_root_lits;
     A.work_counter = st->counter;
     A.lay = lay;
+    const bool wide = ch.kind == SATMI_KERNEL_WIDE;
     if (wide) {
         // one-wave workgroups, each with an HBM arena; resident waves bounded by
         // 32 per CU and by half the free device memory
@@ -1385,24 +1339,25 @@ extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_cl
         set_error("satmi_dpll_batch_host: sol_stride < number of variables");
         return SATMI_ERR_ARG;
     }
-    // one allocation for everything
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_icb = 0;
-    const size_t o_clb = o_icb + up(4 * (size_t)(num_instances + 1));
-    const size_t o_lits = o_clb + up(4 * (size_t)(C + 1));
-    const size_t o_nv = o_lits + up(4 * (size_t)std::max(Ltot, 1));
-    const size_t o_ib = o_nv + up(4 * (size_t)num_instances);
-    const size_t o_il = o_ib + up(4 * (size_t)(num_instances + 1));
-    const size_t o_st = o_il + up(4 * (size_t)std::max(Itot, 1));
-    const size_t o_ctr = o_st + up(4 * (size_t)num_instances);
-    const size_t o_sl = o_ctr + up(8 * (size_t)num_instances * SATMI_NCOUNTERS);
-    const size_t o_sol = o_sl + up(4 * (size_t)num_instances * std::max(sol_cap, 1));
-    const size_t o_rl = o_sol + up(4 * (size_t)num_instances * std::max(sol_cap, 1) * std::max(sol_stride, 1));
-    const size_t o_rlits = o_rl + up(4 * (size_t)num_instances);
-    const size_t total = o_rlits + up(4 * (size_t)num_instances * std::max(sol_stride, 1));
-    unsigned char *d = nullptr;
-    SATMI_HIP(hipMalloc(&d, total));
-    int rc = SATMI_OK;
+    // one allocation for everything, freed on every way out
+    const size_t B = (size_t)num_instances;
+    const size_t cap1 = (size_t)std::max(sol_cap, 1), stride1 = (size_t)std::max(sol_stride, 1);
+    Carve cv;
+    const size_t o_icb = cv.take(4 * (B + 1));
+    const size_t o_clb = cv.take(4 * (size_t)(C + 1));
+    const size_t o_lits = cv.take(4 * (size_t)std::max(Ltot, 1));
+    const size_t o_nv = cv.take(4 * B);
+    const size_t o_ib = cv.take(4 * (B + 1));
+    const size_t o_il = cv.take(4 * (size_t)std::max(Itot, 1));
+    const size_t o_st = cv.take(4 * B);
+    const size_t o_ctr = cv.take(8 * B * SATMI_NCOUNTERS);
+    const size_t o_sl = cv.take(4 * B * cap1);
+    const size_t o_sol = cv.take(4 * B * cap1 * stride1);
+    const size_t o_rl = cv.take(4 * B);
+    const size_t o_rlits = cv.take(4 * B * stride1);
+    DevBuf buf;
+    SATMI_TRY(buf.reserve(cv.at));
+    unsigned char *d = buf.as<unsigned char>();
     hipStream_t s = nullptr;
     auto h2d = [&](size_t off, const void *src, size_t bytes) -> int {
         if (bytes) SATMI_HIP(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, s));
@@ -1412,34 +1367,29 @@ extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_cl
         if (dst && bytes) SATMI_HIP(hipMemcpyAsync(dst, d + off, bytes, hipMemcpyDeviceToHost, s));
         return SATMI_OK;
     };
-    do {
-        if ((rc = h2d(o_icb, h_inst_clause_begin, 4 * (size_t)(num_instances + 1)))) break;
-        if ((rc = h2d(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)))) break;
-        if ((rc = h2d(o_lits, h_lits, 4 * (size_t)Ltot))) break;
-        if ((rc = h2d(o_nv, h_inst_nvars, 4 * (size_t)num_instances))) break;
-        if (h_init_begin) {
-            if ((rc = h2d(o_ib, h_init_begin, 4 * (size_t)(num_instances + 1)))) break;
-            if ((rc = h2d(o_il, h_init_lits, 4 * (size_t)Itot))) break;
-        }
-        rc = satmi_dpll_batch_device(
-            num_instances, (const int32_t *)(d + o_icb), (const int32_t *)(d + o_clb),
-            (const int32_t *)(d + o_lits), (const int32_t *)(d + o_nv), max_vars, max_clauses, max_lits,
-            max_clause_len, h_init_begin ? (const int32_t *)(d + o_ib) : nullptr,
-            h_init_begin ? (const int32_t *)(d + o_il) : nullptr, mode, max_solutions, node_limit,
-            time_limit_s, sol_cap, sol_stride, (int32_t *)(d + o_st), (int64_t *)(d + o_ctr),
-            (int32_t *)(d + o_sl), (int32_t *)(d + o_sol), (int32_t *)(d + o_rl), (int32_t *)(d + o_rlits), s);
-        if (rc) break;
-        if ((rc = d2h(h_status, o_st, 4 * (size_t)num_instances))) break;
-        if ((rc = d2h(h_counters, o_ctr, 8 * (size_t)num_instances * SATMI_NCOUNTERS))) break;
-        if (sol_cap > 0) {
-            if ((rc = d2h(h_sol_len, o_sl, 4 * (size_t)num_instances * sol_cap))) break;
-            if ((rc = d2h(h_sol_lits, o_sol, 4 * (size_t)num_instances * sol_cap * sol_stride))) break;
-        }
-        if ((rc = d2h(h_root_len, o_rl, 4 * (size_t)num_instances))) break;
-        if ((rc = d2h(h_root_lits, o_rlits, 4 * (size_t)num_instances * sol_stride))) break;
-        hipError_t e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-    } while (0);
-    (void)hipFree(d);
-    return rc;
+    SATMI_TRY(h2d(o_icb, h_inst_clause_begin, 4 * (B + 1)));
+    SATMI_TRY(h2d(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)));
+    SATMI_TRY(h2d(o_lits, h_lits, 4 * (size_t)Ltot));
+    SATMI_TRY(h2d(o_nv, h_inst_nvars, 4 * B));
+    if (h_init_begin) {
+        SATMI_TRY(h2d(o_ib, h_init_begin, 4 * (B + 1)));
+        SATMI_TRY(h2d(o_il, h_init_lits, 4 * (size_t)Itot));
+    }
+    SATMI_TRY(satmi_dpll_batch_device(
+        num_instances, (const int32_t *)(d + o_icb), (const int32_t *)(d + o_clb), (const int32_t *)(d + o_lits),
+        (const int32_t *)(d + o_nv), max_vars, max_clauses, max_lits, max_clause_len,
+        h_init_begin ? (const int32_t *)(d + o_ib) : nullptr, h_init_begin ? (const int32_t *)(d + o_il) : nullptr,
+        mode, max_solutions, node_limit, time_limit_s, sol_cap, sol_stride, (int32_t *)(d + o_st),
+        (int64_t *)(d + o_ctr), (int32_t *)(d + o_sl), (int32_t *)(d + o_sol), (int32_t *)(d + o_rl),
+        (int32_t *)(d + o_rlits), s));
+    SATMI_TRY(d2h(h_status, o_st, 4 * B));
+    SATMI_TRY(d2h(h_counters, o_ctr, 8 * B * SATMI_NCOUNTERS));
+    if (sol_cap > 0) {
+        SATMI_TRY(d2h(h_sol_len, o_sl, 4 * B * (size_t)sol_cap));
+        SATMI_TRY(d2h(h_sol_lits, o_sol, 4 * B * (size_t)sol_cap * (size_t)sol_stride));
+    }
+    SATMI_TRY(d2h(h_root_len, o_rl, 4 * B));
+    SATMI_TRY(d2h(h_root_lits, o_rlits, 4 * B * (size_t)sol_stride));
+    const hipError_t e = hipStreamSynchronize(s);
+    return e == hipSuccess ? SATMI_OK : hip_fail(e, "hipStreamSynchronize");
 }

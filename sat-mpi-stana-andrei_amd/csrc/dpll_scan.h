@@ -13,16 +13,43 @@ constexpr int SPLIT_HELPERS_PER_CU = 1;   // measured: 1 best with two pipelined
 // configs[1]) would only ship overhead to the helpers
 constexpr int SPLIT_WARMUP_NODES = 256;
 
-struct ScanLaunch {
-    int num_instances;
+// What the caller of satmi_dpll_batch_device hands over (device pointers), the
+// same for every DPLL kernel: the CSR batch, the limits, the outputs.
+struct DpllBatch {
     const int32_t *inst_clause_begin, *clause_lit_begin, *lits, *inst_nvars;
-    int max_vars, max_clauses, max_lits, max_clause_len;
+    int num_instances, sol_cap, sol_stride;
     int64_t max_solutions, node_limit;
     uint64_t time_limit_ticks;
-    int sol_cap, sol_stride;
     int32_t *status;
     int64_t *counters;
     int32_t *sol_len, *sol_lits, *root_len, *root_lits;
+};
+
+// The batch into a kernel-argument struct (DpllArgs, ScanArgs), by field name:
+// those keep their own member order, which the kernels' code depends on.
+template <class Args>
+void bind_batch(Args &A, const DpllBatch &B) {
+    A.inst_clause_begin = B.inst_clause_begin;
+    A.clause_lit_begin = B.clause_lit_begin;
+    A.lits = B.lits;
+    A.inst_nvars = B.inst_nvars;
+    A.num_instances = B.num_instances;
+    A.sol_cap = B.sol_cap;
+    A.sol_stride = B.sol_stride;
+    A.max_solutions = B.max_solutions;
+    A.node_limit = B.node_limit;
+    A.time_limit_ticks = B.time_limit_ticks;
+    A.status = B.status;
+    A.counters = B.counters;
+    A.sol_len = B.sol_len;
+    A.sol_lits = B.sol_lits;
+    A.root_len = B.root_len;
+    A.root_lits = B.root_lits;
+}
+
+struct ScanLaunch {
+    DpllBatch batch;
+    int max_vars, max_clauses, max_lits, max_clause_len;
     int num_cus;
     // the launch's stream with its work counter and scratch: the occurrence
     // lists of the incremental kernel and the splitting scratch come from it

@@ -1994,8 +1994,6 @@ int lv_static_class(int K, int max_vars) {
     return need <= 512 ? 512 : 2 * (Pack<5>::MAXV + 1);   // 5-SAT n <= 255: 3.5 KB less per wave
 }
 
-uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
-
 // snapshot entries kept in LDS: all with byte codes, at most 512 with 16-bit
 // codes (the rest in HBM: snap_put); M = clauses + 1
 // snapshot entries in LDS: all (byte codes), else the first 256 for 3-literal
@@ -2037,7 +2035,7 @@ bool make_layout(int K, int max_vars, int max_clauses, bool with_lv, bool inc, u
     lay->mcap = max_clauses;
     lay->ncap = max_vars;
     lay->nw = (int32_t)NW;
-    return o <= 160u * 1024u;
+    return o <= LDS_PER_CU;
 }
 
 // The kernel forms: one row per (K, static literal-state class; 0 = lv in the
@@ -2112,8 +2110,8 @@ int scan_plan(int K, int max_vars, int max_clauses, bool inc, ScanPlan *P) {
         if (!fn) continue;
         const uint32_t wg_lds = lay.bytes * (uint32_t)wpg;
         const uint32_t wg_all = wg_lds + (uint32_t)lvs;
-        if (wg_all > 160u * 1024u) continue;
-        int wgs = std::min(32 / wpg, (int)((160u * 1024u) / wg_all));
+        if (wg_all > LDS_PER_CU) continue;
+        int wgs = std::min(32 / wpg, (int)(LDS_PER_CU / wg_all));
         if (wg_lds > 64u * 1024u)
             SATMI_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds));
         int occ = 0;
@@ -2205,33 +2203,15 @@ int dpll_scan_launch(const ScanLaunch &L) {
     const ScanLayout &lay = P.lay;
     const int waves_per_wg = P.waves_per_wg;
     const uint32_t wg_lds = lay.bytes * (uint32_t)waves_per_wg;
-    const int need = (L.num_instances + waves_per_wg - 1) / waves_per_wg;
+    const int num_instances = L.batch.num_instances;
+    const int need = (num_instances + waves_per_wg - 1) / waves_per_wg;
     int grid = std::max(1, std::min(need, L.num_cus * P.wg_per_cu));
 
-    ScanArgs A;
-    A.inst_clause_begin = L.inst_clause_begin;
-    A.clause_lit_begin = L.clause_lit_begin;
-    A.lits = L.lits;
-    A.inst_nvars = L.inst_nvars;
-    A.num_instances = L.num_instances;
-    A.sol_cap = L.sol_cap;
-    A.sol_stride = L.sol_stride;
-    A.max_solutions = L.max_solutions;
-    A.node_limit = L.node_limit;
-    A.time_limit_ticks = L.time_limit_ticks;
-    A.status = L.status;
-    A.counters = L.counters;
-    A.sol_len = L.sol_len;
-    A.sol_lits = L.sol_lits;
-    A.root_len = L.root_len;
-    A.root_lits = L.root_lits;
+    ScanArgs A{};   // occ, occ_cap, occ_lists, split: none until taken below
+    bind_batch(A, L.batch);
     A.work_counter = L.st->counter;
-    A.occ = nullptr;
-    A.occ_cap = 0;
-    A.occ_lists = 0;
     A.snap_lds = P.fixed ? 0u : snap_lds_entries(K, P.lvs == 256 ? 1u : 2u, (uint32_t)lay.mcap + 1u);
     A.lay = lay;
-    A.split = nullptr;
     // split only where the launch's tail matters: at most SPLIT_MAX_PER_WAVE
     // instances per resident wave (at 32 per wave the tail is a few percent and
     // the two-stream pipeline hides it; the split form's register cost is not;
@@ -2242,8 +2222,8 @@ int dpll_scan_launch(const ScanLaunch &L) {
     // from the start -- configs[1]: 4,096 short searches -- loses 7 % to the
     // split form and gains nothing: the other stream's launch fills those slots)
     const int64_t waves = (int64_t)grid * waves_per_wg;
-    const bool few = L.split_always || ((int64_t)L.num_instances <= (int64_t)SPLIT_MAX_PER_WAVE * waves &&
-                                        (int64_t)L.num_instances >= (int64_t)L.num_cus * P.wg_per_cu * waves_per_wg);
+    const bool few = L.split_always || ((int64_t)num_instances <= (int64_t)SPLIT_MAX_PER_WAVE * waves &&
+                                        (int64_t)num_instances >= (int64_t)L.num_cus * P.wg_per_cu * waves_per_wg);
     if (L.split && few) {
         // slot pool: trail codes of the launch's entry width; one donation-stack
         // entry per decision frame per resident wave
@@ -2267,7 +2247,7 @@ int dpll_scan_launch(const ScanLaunch &L) {
         // instances find the queue empty and register as helpers at once, so
         // the hard searches' subtrees spread over idle CU slots instead of
         // waiting for the easy instances to finish
-        const int64_t with_helpers = ((int64_t)L.num_instances + cfg.max_helpers + waves_per_wg - 1) / waves_per_wg;
+        const int64_t with_helpers = ((int64_t)num_instances + cfg.max_helpers + waves_per_wg - 1) / waves_per_wg;
         grid = (int)std::max<int64_t>(grid, std::min<int64_t>(with_helpers, (int64_t)L.num_cus * P.wg_per_cu));
         const size_t pool = (size_t)cfg.slot_cap * (size_t)cfg.slot_bytes;
         const size_t stacks = (size_t)grid * (size_t)waves_per_wg * (size_t)cfg.dstack_cap * sizeof(int32_t);

@@ -1,10 +1,11 @@
 // host.h -- the host-side layer the solver translation units share (dpll.hip,
 // dpll_scan.hip, dp.hip, resolution.hip, cdcl.hip, resolution_batch.hip,
-// dp_batch.hip): the error-propagating SATMI_TRY, the cached device facts, the
-// grow-only device and pinned buffers, the workspace pool with its lease, the
-// dense variable index, and the DPLL launches' per-stream state (the two batched
-// entry points share batch_keys.h and batch_host.h besides).  Host code only;
-// device helpers are in common.h.
+// dp_batch.hip): the error-propagating SATMI_TRY, a CU's LDS size, the alignment
+// and carving of layouts, the cached device facts, the grow-only device and
+// pinned buffers, the workspace pool with its lease, the dense variable index,
+// and the DPLL launches' per-stream state (the two batched entry points share
+// batch_keys.h and batch_host.h besides).  Host code only; device helpers are
+// in common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +26,22 @@ namespace satmi {
         int _rc = (x);                   \
         if (_rc != SATMI_OK) return _rc; \
     } while (0)
+
+constexpr uint32_t LDS_PER_CU = 160u * 1024u;   // bytes of LDS a CU's workgroups share
+
+// Layout builders place their arrays on 16-byte boundaries.
+template <class U>
+constexpr U align16(U x) { return (x + 15u) & ~(U)15u; }
+
+// Offsets of the arrays of one block, each 256-byte aligned; `at` ends as its size.
+struct Carve {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t off = at;
+        at += (bytes + 255) & ~(size_t)255;
+        return off;
+    }
+};
 
 // ---------------------------------------------------------------- device facts
 // What the launch paths ask about the current device, queried once per device.
