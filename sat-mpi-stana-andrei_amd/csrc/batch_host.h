@@ -12,16 +12,10 @@ namespace satmi {
 // A call's device state, kept between calls in the workspace pool (host.h; one
 // pool per entry point: each derives its own empty type).  Nothing in it is
 // trusted by the next call, so it goes back to the pool whatever the outcome.
-struct BatchWork {
+struct BatchWork : WorkStream {
     DevBuf up, out;     // the inputs, one upload; the outputs, zeroed, one copy back
     DevBuf keys_out, rec_off;   // record: the keys the kernel keeps; where each formula's go (Davis-Putnam)
     PinBuf up_h, out_h;
-    hipStream_t stream = nullptr;
-    int dev = 0;
-    ~BatchWork() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    bool open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
     void drop_large_record() {   // its keys are not kept in the pool past a large recorded batch
         if (keys_out.cap > ((size_t)64 << 20)) keys_out.release();
     }

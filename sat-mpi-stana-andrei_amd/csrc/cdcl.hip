@@ -940,14 +940,8 @@ bool make_cdcl_layout(int max_vars, int64_t max_clauses, int64_t max_lits, int m
 // threads overlap on the device, so the waves a batch's few long solves leave
 // idle run another batch.  A slot's memory carries nothing between calls, so a
 // failed call returns its slot like any other, and no slot is ever destroyed.
-struct CdclSlot {
-    int dev = 0;
+struct CdclSlot : WorkStream {
     DevBuf mem;
-    hipStream_t stream = nullptr;
-    ~CdclSlot() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    bool open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
 };
 // The calling thread's last satmi_cdcl_batch_host launch (satmi_cdcl_last_stats).
 struct CdclStats {

@@ -54,6 +54,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -1596,8 +1597,22 @@ namespace {
 // The buffers grow step by step with the elimination (DevBuf::grow).
 constexpr OomText DP_OOM{"satmi_dp_host", "bound the elimination with clause_limit"};
 
+// How many items fit every buffer of a set: the minimum over (buffer, bytes per item).
+struct Sized {
+    const DevBuf &buf;
+    size_t item;
+};
+int64_t items_cap(std::initializer_list<Sized> set) {
+    int64_t c = INT64_MAX;
+    for (const Sized &x : set) c = std::min<int64_t>(c, (int64_t)(x.buf.cap / x.item));
+    return c;
+}
+
 struct Gen {   // one generation's per-clause arrays
     DevBuf off, mask, fill, used, bits;
+    int64_t cap(int K) const {   // clauses they all hold
+        return items_cap({{off, 8}, {mask, 4}, {fill, 4}, {used, 4}, {bits, 8 * (size_t)K}});
+    }
     int reserve(int64_t n, int K, hipStream_t s, int64_t keep_n) {
         n = std::max<int64_t>(n, 1);
         SATMI_TRY(off.grow(8 * (size_t)n, s, &DP_OOM, 8 * (size_t)keep_n));
@@ -1621,23 +1636,11 @@ struct DpStats {
 };
 thread_local DpStats g_dp_stats;   // the calling thread's last call
 
-// The captured step batch of a workspace (see satmi_dp_host).
-struct DpGraph {
-    hipGraphExec_t exec = nullptr;
-    DpArgs args;
-    int batch = 0;
-    DpGraph() { std::memset(&args, 0, sizeof(args)); }
-    void reset() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        exec = nullptr;
-        batch = 0;
-    }
-};
 
 // Device buffers of one solve, kept between calls (grow-only) in the workspace
 // pool (host.h).  A call that failed part-way destroys its workspace: its
 // device state -- epoch stamps, the hash table -- may not be clean.
-struct DpWork {
+struct DpWork : WorkStream {
     DevBuf d_off, d_lits, d_v2d, d_d2v, state, firstpos, order, popscratch, trace;
     DevBuf plist, nlist, rlist, rbits, ntbits, table, uslot, dropped, hit, surv, klist, keptbits, xs, arena;
     DevBuf rkeys, skeys, ustage, stripes;
@@ -1646,23 +1649,13 @@ struct DpWork {
     uint64_t tslots = 0;
     int K = 0;
     int32_t epoch = 0;
-    DpArgs hint_args;             // the last completed call's arguments and step slots used
+    DpArgs hint_args;    // the last completed call's arguments and step slots used
     int hint_slots = 0;
-    std::vector<hipEvent_t> ev;   // filter timing: one pair per step, read once per call
-    hipStream_t stream = nullptr;
-    DpState *pin = nullptr;       // pinned host copy of the state
-    int dev = 0;
-    DpGraph graph;
-    ~DpWork() {   // only a workspace that failed mid-call (or a trim) destroys one, after its stream drained
-        graph.reset();
-        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (pin) (void)hipHostFree(pin);
-    }
-    bool open() {
-        return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
-               hipHostMalloc((void **)&pin, sizeof(DpState), hipHostMallocDefault) == hipSuccess;
-    }
+    PinBuf pin;          // pinned host copy of the state
+    EventTimer timer;    // device time of the elimination steps: one event pair per batch
+    ReplayGraph graph;   // the captured step batch (see dp_eliminate)
+    bool open() { return WorkStream::open() && pin.reserve(sizeof(DpState)) == SATMI_OK; }
+    DpState &st() { return *(DpState *)pin.p; }
 };
 
 // grow the pair-sized buffers (contents are per-step scratch; the stamp
@@ -1694,11 +1687,10 @@ int grow_pairs(DpWork &W, int64_t npairs, int K) {
     uint64_t pw = 1024;
     while (pw * 2 <= W.table.cap / 8) pw <<= 1;
     W.tslots = pw;
-    W.pair_cap = std::min<int64_t>((int64_t)(W.rbits.cap / (8 * (size_t)K)), (int64_t)(W.tslots / 2));
-    W.pair_cap = std::min<int64_t>(W.pair_cap, (int64_t)(W.uslot.cap / 4));
-    W.pair_cap = std::min<int64_t>(W.pair_cap, (int64_t)(W.ustage.cap / (4 * (size_t)DP_STRIPES)));
-    W.pair_cap = std::min<int64_t>(W.pair_cap, (int64_t)(W.skeys.cap / (8 * (size_t)K)));
-    W.pair_cap = std::min<int64_t>(W.pair_cap, (1ll << 31) - 1);
+    const size_t key = 8 * (size_t)K;
+    W.pair_cap = std::min<int64_t>(
+        {items_cap({{W.rbits, key}, {W.uslot, 4}, {W.ustage, 4 * (size_t)DP_STRIPES}, {W.skeys, key}}),
+         (int64_t)(W.tslots / 2), (1ll << 31) - 1});
     W.K = K;
     return SATMI_OK;
 }
@@ -1713,20 +1705,283 @@ int grow_ncl(DpWork &W, int64_t n, int K, int cur, int64_t keep_n) {
     SATMI_TRY(W.nlist.grow(8 * (size_t)cap, s, &DP_OOM));
     SATMI_TRY(W.rlist.grow(8 * (size_t)cap, s, &DP_OOM));
     SATMI_TRY(W.rkeys.grow(8 * (size_t)cap * K, s, &DP_OOM));
-    int64_t c = INT64_MAX;
-    for (int g = 0; g < 2; ++g) {
-        c = std::min<int64_t>(c, (int64_t)(W.g[g].off.cap / 8));
-        c = std::min<int64_t>(c, (int64_t)(W.g[g].mask.cap / 4));
-        c = std::min<int64_t>(c, (int64_t)(W.g[g].fill.cap / 4));
-        c = std::min<int64_t>(c, (int64_t)(W.g[g].used.cap / 4));
-        c = std::min<int64_t>(c, (int64_t)(W.g[g].bits.cap / (8 * (size_t)K)));
-    }
-    c = std::min<int64_t>(c, (int64_t)(W.plist.cap / 8));
-    c = std::min<int64_t>(c, (int64_t)(W.nlist.cap / 8));
-    c = std::min<int64_t>(c, (int64_t)(W.rlist.cap / 8));
-    c = std::min<int64_t>(c, (int64_t)(W.rkeys.cap / (8 * (size_t)K)));
-    W.ncl_cap = c;
+    W.ncl_cap = std::min<int64_t>(
+        {W.g[0].cap(K), W.g[1].cap(K),
+         items_cap({{W.plist, 8}, {W.nlist, 8}, {W.rlist, 8}, {W.rkeys, 8 * (size_t)K}})});
     return SATMI_OK;
+}
+
+// What a call fixes before its first step.
+struct DpCall {
+    int nclauses;
+    const int32_t *off, *lits;   // the caller's CSR formula
+    int64_t Ltot;
+    int maxvar, V, Wd, K;
+    int64_t cap0, popcap, arena0;   // a clause's set slots; the pop scratch's; the encoded formula's arena words
+    int64_t step_limit, clause_limit;
+    uint64_t limit_ticks;
+    int inline_steps;
+};
+
+// The caller's recording arrays (all three, or no recording) and how far they
+// are filled: the clause list after every step, a step's clauses ending at
+// step_off[step].
+struct DpRecord {
+    int32_t *lits;
+    int64_t lit_cap;
+    int64_t *clause_off;
+    int64_t clause_cap;
+    int64_t *step_off;
+    int step_cap;
+    int64_t clauses = 0, nlits = 0;
+    int steps = 0;
+    std::vector<int64_t> h_off;   // a step's clause list on the host
+    std::vector<int32_t> h_mask, h_arena;
+    bool on() const { return lits && clause_off && step_off; }
+};
+
+// Size the workspace for the formula and send it with the start state.
+int dp_upload(DpWork &Wk, const DpCall &c, const std::vector<int32_t> &var2dense,
+              const std::vector<int32_t> &dense2var) {
+    hipStream_t s = Wk.stream;
+    const int V = c.V;
+    if (Wk.K != c.K) {   // key width changed: every K-sized buffer is re-laid out
+        Wk.ncl_cap = 0;
+        Wk.pair_cap = 0;
+    }
+    SATMI_TRY(Wk.d_off.grow(4 * (size_t)(c.nclauses + 1), s, &DP_OOM));
+    SATMI_TRY(Wk.d_lits.grow(4 * (size_t)std::max<int64_t>(c.Ltot, 1), s, &DP_OOM));
+    SATMI_TRY(Wk.d_v2d.grow(4 * (size_t)(c.maxvar + 1), s, &DP_OOM));
+    SATMI_TRY(Wk.d_d2v.grow(4 * (size_t)V, s, &DP_OOM));
+    SATMI_TRY(Wk.state.grow(sizeof(DpState), s, &DP_OOM));
+    SATMI_TRY(Wk.firstpos.grow(8 * (size_t)V, s, &DP_OOM));
+    SATMI_TRY(Wk.order.grow(4 * (size_t)V, s, &DP_OOM));
+    SATMI_TRY(Wk.popscratch.grow(4 * (size_t)2 * c.popcap, s, &DP_OOM));
+    SATMI_TRY(Wk.trace.grow(4 * (size_t)(V + 1), s, &DP_OOM));
+    SATMI_TRY(Wk.stripes.grow(8 * 3 * DP_STRIPES, s, &DP_OOM, 0, 0));
+    SATMI_TRY(grow_ncl(Wk, std::max<int64_t>(c.nclauses, 1), c.K, 0, 0));
+    SATMI_TRY(grow_pairs(Wk, 1, c.K));
+    SATMI_TRY(Wk.arena.grow(4 * (size_t)std::max<int64_t>(c.arena0 * 4, 1 << 16), s, &DP_OOM));
+    Wk.arena_cap = (int64_t)(Wk.arena.cap / 4);
+    SATMI_TRY(Wk.xs.grow(4 * (size_t)(1 << 16), s, &DP_OOM));
+    Wk.xs_cap = (int64_t)(Wk.xs.cap / 4);
+
+    if (c.nclauses > 0) {
+        SATMI_HIP(hipMemcpyAsync(Wk.d_off.p, c.off, 4 * (size_t)(c.nclauses + 1), hipMemcpyHostToDevice, s));
+        if (c.Ltot) SATMI_HIP(hipMemcpyAsync(Wk.d_lits.p, c.lits, 4 * (size_t)c.Ltot, hipMemcpyHostToDevice, s));
+    }
+    SATMI_HIP(hipMemcpyAsync(Wk.d_v2d.p, var2dense.data(), 4 * (size_t)(c.maxvar + 1), hipMemcpyHostToDevice, s));
+    SATMI_HIP(hipMemcpyAsync(Wk.d_d2v.p, dense2var.data(), 4 * (size_t)V, hipMemcpyHostToDevice, s));
+    SATMI_HIP(hipMemsetAsync(Wk.firstpos.p, 0xFF, 8 * (size_t)V, s));
+    DpState &st = Wk.st();
+    st = DpState{};
+    st.ncl = c.nclauses;
+    st.arena_top = c.arena0;
+    st.first_empty = DP_EMPTY;
+    st.epoch = Wk.epoch;
+    SATMI_HIP(hipMemcpyAsync(Wk.state.p, Wk.pin.p, sizeof(DpState), hipMemcpyHostToDevice, s));
+    return SATMI_OK;
+}
+
+// The kernels' arguments: the workspace as it is now and the call's limits.
+DpArgs dp_args(const DpWork &Wk, const DpCall &c) {
+    DpArgs a;
+    std::memset(&a, 0, sizeof(a));   // padding too: a batch's graph is keyed by these bytes
+    a.st = Wk.state.as<DpState>();
+    a.g[0] = Wk.g[0].view();
+    a.g[1] = Wk.g[1].view();
+    a.arena = Wk.arena.as<int32_t>();
+    a.arena_cap = Wk.arena_cap;
+    a.v2d = Wk.d_v2d.as<int32_t>();
+    a.d2v = Wk.d_d2v.as<int32_t>();
+    a.V = c.V;
+    a.W = c.Wd;
+    a.K = c.K;
+    a.firstpos = Wk.firstpos.as<unsigned long long>();
+    a.order = Wk.order.as<int32_t>();
+    a.popscratch = Wk.popscratch.as<int32_t>();
+    a.popcap = c.popcap;
+    a.plist = Wk.plist.as<int64_t>();
+    a.nlist = Wk.nlist.as<int64_t>();
+    a.rlist = Wk.rlist.as<int64_t>();
+    a.ncl_cap = Wk.ncl_cap;
+    a.rbits = Wk.rbits.as<uint64_t>();
+    a.ntbits = Wk.ntbits.as<uint64_t>();
+    a.pair_cap = Wk.pair_cap;
+    a.table = Wk.table.as<uint64_t>();
+    a.tmask = Wk.tslots - 1;
+    a.uslot = Wk.uslot.as<uint32_t>();
+    a.dropped = Wk.dropped.as<int32_t>();
+    a.hit = Wk.hit.as<int32_t>();
+    a.surv = Wk.surv.as<uint32_t>();
+    a.klist = Wk.klist.as<uint32_t>();
+    a.rkeys = Wk.rkeys.as<uint64_t>();
+    a.skeys = Wk.skeys.as<uint64_t>();
+    a.stripes = Wk.stripes.as<unsigned long long>();
+    a.ustage = Wk.ustage.as<uint32_t>();
+    a.keptbits = Wk.keptbits.as<uint32_t>();
+    a.xs = Wk.xs.as<int32_t>();
+    a.xs_cap = Wk.xs_cap;
+    a.trace = Wk.trace.as<int32_t>();
+    a.trace_cap = c.V + 1;
+    a.step_limit = c.step_limit;
+    a.clause_limit = c.clause_limit;
+    a.limit_ticks = c.limit_ticks;
+    a.inline_steps = c.inline_steps;
+    return a;
+}
+
+// f(std::integral_constant<int, KT>{}) for the filter kernels' instance of K key
+// words: 2, 4, 6, 8, or 0 (K read at run time).
+template <class F>
+void dp_with_width(int K, F &&f) {
+    switch (K) {
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, 0>{});
+    }
+}
+
+// one elimination step: DP_LAUNCHES_PER_STEP launches, sizes on the device
+int dp_enqueue_step(const DpArgs &a, hipStream_t s) {
+    const int gp = (int)std::min<int64_t>(DP_GRID_PAIRS, (a.pair_cap + 255) / 256);
+    const int gc = (int)std::min<int64_t>(DP_GRID_ASM, (a.ncl_cap + ASM_WAVES - 1) / ASM_WAVES);
+    if (a.inline_steps > 0) hipLaunchKernelGGL(dp_pop_split_kernel<true>, dim3(1), dim3(POP_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(dp_pop_split_kernel<false>, dim3(1), dim3(POP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(dp_pairs_kernel, dim3(gp), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(dp_hash_kernel, dim3(gp), dim3(256), 0, s, a);
+    const dim3 gt((unsigned)std::min<int64_t>(DP_GRID_TEST, std::max<int64_t>(64, a.pair_cap / 256)));
+    dp_with_width(a.K, [&](auto kt) {
+        hipLaunchKernelGGL(dp_remtest_kernel<decltype(kt)::value>, gt, dim3(TEST_TILE), 0, s, a);
+    });
+    hipLaunchKernelGGL(dp_survlist_kernel, dim3(gp), dim3(256), 0, s, a);
+    dp_with_width(a.K, [&](auto kt) {
+        hipLaunchKernelGGL(dp_survtest_kernel<decltype(kt)::value>, gt, dim3(TEST_TILE), 0, s, a);
+    });
+    hipLaunchKernelGGL(dp_kept_kernel, dim3(1), dim3(POP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(dp_assemble_kernel, dim3(gc), dim3(64 * ASM_WAVES), 0, s, a);
+    SATMI_HIP(hipGetLastError());
+    return SATMI_OK;
+}
+
+// After an overflow: grow what ran out, send the state back with the flags
+// cleared, and rebuild the first positions -- the step then runs again.
+int dp_resume(DpWork &Wk, const DpCall &c, DpArgs &A) {
+    hipStream_t s = Wk.stream;
+    DpState &st = Wk.st();
+    for (int b = 0; b < 4; ++b) g_dp_stats.resumes[b] += (st.overflow >> b) & 1;
+    if (st.overflow & OVF_PAIRS) SATMI_TRY(grow_pairs(Wk, st.need[0], c.K));
+    if (st.overflow & OVF_NCL) SATMI_TRY(grow_ncl(Wk, st.need[1], c.K, st.cur, st.ncl));
+    if (st.overflow & OVF_ARENA) {
+        SATMI_TRY(Wk.arena.grow(4 * (size_t)st.need[2], s, &DP_OOM, 4 * (size_t)st.arena_top));
+        Wk.arena_cap = (int64_t)(Wk.arena.cap / 4);
+    }
+    if (st.overflow & OVF_XS) {
+        SATMI_TRY(Wk.xs.grow(4 * (size_t)st.need[3], s, &DP_OOM));
+        Wk.xs_cap = (int64_t)(Wk.xs.cap / 4);
+    }
+    st.overflow = 0;
+    st.done = 0;
+    SATMI_HIP(hipMemcpyAsync(Wk.state.p, Wk.pin.p, sizeof(DpState), hipMemcpyHostToDevice, s));
+    A = dp_args(Wk, c);
+    SATMI_HIP(hipMemsetAsync(Wk.firstpos.p, 0xFF, 8 * (size_t)c.V, s));
+    hipLaunchKernelGGL(dp_firstpos_kernel, dim3(grid_for(std::max<int64_t>(st.ncl, 1))), dim3(256), 0, s, A);
+    SATMI_HIP(hipGetLastError());
+    return SATMI_OK;
+}
+
+// The clause list after the step just run, each clause in its set iteration
+// order; past lit_cap literals are dropped one by one.
+int dp_record_step(DpWork &Wk, DpRecord &rec) {
+    hipStream_t s = Wk.stream;
+    const DpState &st = Wk.st();
+    const int64_t n2 = st.ncl2;
+    const int nxt = st.cur ^ 1;
+    rec.h_off.resize((size_t)std::max<int64_t>(n2, 1));
+    rec.h_mask.resize((size_t)std::max<int64_t>(n2, 1));
+    rec.h_arena.resize((size_t)std::max<int64_t>(st.arena_top, 1));
+    if (n2 > 0) {
+        SATMI_HIP(hipMemcpyAsync(rec.h_off.data(), Wk.g[nxt].off.p, 8 * (size_t)n2, hipMemcpyDeviceToHost, s));
+        SATMI_HIP(hipMemcpyAsync(rec.h_mask.data(), Wk.g[nxt].mask.p, 4 * (size_t)n2, hipMemcpyDeviceToHost, s));
+        SATMI_HIP(hipMemcpyAsync(rec.h_arena.data(), Wk.arena.p, 4 * (size_t)st.arena_top, hipMemcpyDeviceToHost, s));
+        SATMI_HIP(hipStreamSynchronize(s));
+    }
+    for (int64_t c = 0; c < n2 && rec.clauses + 1 < rec.clause_cap; ++c) {
+        for (int64_t i = 0; i <= rec.h_mask[c]; ++i) {
+            const int32_t k = rec.h_arena[rec.h_off[c] + i];
+            if (k != PY_EMPTY && k != PY_DUMMY && rec.nlits < rec.lit_cap) rec.lits[rec.nlits++] = k;
+        }
+        rec.clause_off[++rec.clauses] = rec.nlits;
+    }
+    rec.step_off[st.steps] = rec.clauses;
+    rec.steps = st.steps;
+    return SATMI_OK;
+}
+
+struct DpGraphKey {   // what a batch's launches read from the host
+    DpArgs args;
+    int batch;
+};
+
+// The elimination: batches of steps, the state back after each, until done.
+int dp_eliminate(DpWork &Wk, const DpCall &c, DpRecord &rec, DpArgs &A) {
+    hipStream_t s = Wk.stream;
+    const DpState &st = Wk.st();
+    const bool record = rec.on();
+    const int V = c.V;
+    int enqueued = 0;   // steps enqueued since the last resume
+    bool first_batch = true;
+    Wk.timer.reset();
+    for (;;) {
+        // at most V steps eliminate a variable, then one pop finds the set empty;
+        // a slot may run many steps inline, so a call with the arguments of the
+        // last one starts with as many slots as that one used (the next batch,
+        // if any, with the full count)
+        const bool hinted = first_batch && Wk.hint_slots > 0 && std::memcmp(&Wk.hint_args, &A, sizeof(DpArgs)) == 0;
+        const int batch = record ? 1 : hinted ? std::min(Wk.hint_slots, V + 1) : std::min(64, V + 1);
+        first_batch = false;
+        const auto enqueue_batch = [&]() -> int {
+            int rc = SATMI_OK;
+            for (int k = 0; k < batch && rc == SATMI_OK; ++k) rc = dp_enqueue_step(A, s);
+            return rc;
+        };
+        SATMI_TRY(Wk.timer.begin(s, "satmi_dp_host"));
+        // A batch is ~10 launches per step whose arguments depend only on the
+        // workspace and the call's limits: the second time the same batch is
+        // enqueued it is captured into a HIP graph, and from then on replayed
+        // with one launch (the steps' sizes live on the device either way).
+        if (record) {
+            SATMI_TRY(enqueue_batch());
+        } else {
+            DpGraphKey key;
+            std::memset(&key, 0, sizeof(key));
+            key.args = A;
+            key.batch = batch;
+            SATMI_TRY(Wk.graph.run(s, key, enqueue_batch));
+        }
+        SATMI_TRY(Wk.timer.end(s, "satmi_dp_host"));
+        enqueued += batch;
+        g_dp_stats.launches += (int64_t)batch * DP_LAUNCHES_PER_STEP;
+        SATMI_HIP(hipMemcpyAsync(Wk.pin.p, Wk.state.p, sizeof(DpState), hipMemcpyDeviceToHost, s));
+        SATMI_HIP(hipStreamSynchronize(s));
+        if (st.set_ovf) {
+            set_error("satmi_dp_host: set model table overflow");
+            return SATMI_ERR_TOO_LARGE;
+        }
+        if (st.overflow) {
+            SATMI_TRY(dp_resume(Wk, c, A));
+            enqueued = 0;
+            continue;
+        }
+        if (record && st.pending && st.steps > rec.steps && st.steps < rec.step_cap) SATMI_TRY(dp_record_step(Wk, rec));
+        if (st.done) return SATMI_OK;
+        if (enqueued > V + 1) {   // cannot happen: every step eliminates a variable
+            set_error("satmi_dp_host: elimination did not terminate");
+            return SATMI_ERR_HIP;
+        }
+    }
 }
 
 }  // namespace
@@ -1772,256 +2027,37 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
     }
     DpWork &Wk = *lease.w;
     hipStream_t s = Wk.stream;
-    if (Wk.K != K) {   // key width changed: every K-sized buffer is re-laid out
-        Wk.ncl_cap = 0;
-        Wk.pair_cap = 0;
-    }
-    const int64_t cap0 = cap_for(maxlen);
-    SATMI_TRY(Wk.d_off.grow(4 * (size_t)(nclauses + 1), s, &DP_OOM));
-    SATMI_TRY(Wk.d_lits.grow(4 * (size_t)std::max<int64_t>(Ltot, 1), s, &DP_OOM));
-    SATMI_TRY(Wk.d_v2d.grow(4 * (size_t)(maxvar + 1), s, &DP_OOM));
-    SATMI_TRY(Wk.d_d2v.grow(4 * (size_t)V, s, &DP_OOM));
-    SATMI_TRY(Wk.state.grow(sizeof(DpState), s, &DP_OOM));
-    SATMI_TRY(Wk.firstpos.grow(8 * (size_t)V, s, &DP_OOM));
-    SATMI_TRY(Wk.order.grow(4 * (size_t)V, s, &DP_OOM));
-    const int64_t popcap = cap_for(V);
-    SATMI_TRY(Wk.popscratch.grow(4 * (size_t)2 * popcap, s, &DP_OOM));
-    SATMI_TRY(Wk.trace.grow(4 * (size_t)(V + 1), s, &DP_OOM));
-    SATMI_TRY(Wk.stripes.grow(8 * 3 * DP_STRIPES, s, &DP_OOM, 0, 0));
-    SATMI_TRY(grow_ncl(Wk, std::max<int64_t>(nclauses, 1), K, 0, 0));
-    SATMI_TRY(grow_pairs(Wk, 1, K));
-    const int64_t arena0 = (int64_t)nclauses * 2 * cap0;
-    SATMI_TRY(Wk.arena.grow(4 * (size_t)std::max<int64_t>(arena0 * 4, 1 << 16), s, &DP_OOM));
-    Wk.arena_cap = (int64_t)(Wk.arena.cap / 4);
-    SATMI_TRY(Wk.xs.grow(4 * (size_t)(1 << 16), s, &DP_OOM));
-    Wk.xs_cap = (int64_t)(Wk.xs.cap / 4);
-
-    if (nclauses > 0) {
-        SATMI_HIP(hipMemcpyAsync(Wk.d_off.p, h_clause_off, 4 * (size_t)(nclauses + 1), hipMemcpyHostToDevice, s));
-        if (Ltot) SATMI_HIP(hipMemcpyAsync(Wk.d_lits.p, h_lits, 4 * (size_t)Ltot, hipMemcpyHostToDevice, s));
-    }
-    SATMI_HIP(hipMemcpyAsync(Wk.d_v2d.p, var2dense.data(), 4 * (size_t)(maxvar + 1), hipMemcpyHostToDevice, s));
-    SATMI_HIP(hipMemcpyAsync(Wk.d_d2v.p, dense2var.data(), 4 * (size_t)V, hipMemcpyHostToDevice, s));
-    SATMI_HIP(hipMemsetAsync(Wk.firstpos.p, 0xFF, 8 * (size_t)V, s));
-    DpState &st = *Wk.pin;
-    st = DpState{};
-    st.ncl = nclauses;
-    st.arena_top = arena0;
-    st.first_empty = DP_EMPTY;
-    st.epoch = Wk.epoch;
-    SATMI_HIP(hipMemcpyAsync(Wk.state.p, Wk.pin, sizeof(DpState), hipMemcpyHostToDevice, s));
-
-    const bool record = h_rec_lits && h_rec_clause_off && h_rec_step_off;
+    DpRecord rec{h_rec_lits, rec_lit_cap, h_rec_clause_off, rec_clause_cap, h_rec_step_off, rec_step_cap};
     const char *inl_env = std::getenv("SATMI_DP_INLINE");
     const bool inline_on = inl_env && inl_env[0] == '1';
-    const auto args = [&]() {
-        DpArgs a;
-        std::memset(&a, 0, sizeof(a));   // padding too: a batch's graph is keyed by these bytes
-        a.st = Wk.state.as<DpState>();
-        a.g[0] = Wk.g[0].view();
-        a.g[1] = Wk.g[1].view();
-        a.arena = Wk.arena.as<int32_t>();
-        a.arena_cap = Wk.arena_cap;
-        a.v2d = Wk.d_v2d.as<int32_t>();
-        a.d2v = Wk.d_d2v.as<int32_t>();
-        a.V = V;
-        a.W = Wd;
-        a.K = K;
-        a.firstpos = Wk.firstpos.as<unsigned long long>();
-        a.order = Wk.order.as<int32_t>();
-        a.popscratch = Wk.popscratch.as<int32_t>();
-        a.popcap = popcap;
-        a.plist = Wk.plist.as<int64_t>();
-        a.nlist = Wk.nlist.as<int64_t>();
-        a.rlist = Wk.rlist.as<int64_t>();
-        a.ncl_cap = Wk.ncl_cap;
-        a.rbits = Wk.rbits.as<uint64_t>();
-        a.ntbits = Wk.ntbits.as<uint64_t>();
-        a.pair_cap = Wk.pair_cap;
-        a.table = Wk.table.as<uint64_t>();
-        a.tmask = Wk.tslots - 1;
-        a.uslot = Wk.uslot.as<uint32_t>();
-        a.dropped = Wk.dropped.as<int32_t>();
-        a.hit = Wk.hit.as<int32_t>();
-        a.surv = Wk.surv.as<uint32_t>();
-        a.klist = Wk.klist.as<uint32_t>();
-        a.rkeys = Wk.rkeys.as<uint64_t>();
-        a.skeys = Wk.skeys.as<uint64_t>();
-        a.stripes = Wk.stripes.as<unsigned long long>();
-        a.ustage = Wk.ustage.as<uint32_t>();
-        a.keptbits = Wk.keptbits.as<uint32_t>();
-        a.xs = Wk.xs.as<int32_t>();
-        a.xs_cap = Wk.xs_cap;
-        a.trace = Wk.trace.as<int32_t>();
-        a.trace_cap = V + 1;
-        a.step_limit = step_limit;
-        a.clause_limit = clause_limit;
-        a.limit_ticks = time_limit_s > 0 ? (uint64_t)std::max(1.0, time_limit_s * hz) : 0;
-        // inline steps (opt-in); recording reads the clause list after every
-        // step: one step per slot
-        a.inline_steps = !inline_on ? 0 : record ? 1 : (1 << 30);
-        return a;
-    };
-    DpArgs A = args();
+    const int64_t cap0 = cap_for(maxlen);
+    DpCall c{};
+    c.nclauses = nclauses;
+    c.off = h_clause_off;
+    c.lits = h_lits;
+    c.Ltot = Ltot;
+    c.maxvar = maxvar;
+    c.V = V;
+    c.Wd = Wd;
+    c.K = K;
+    c.cap0 = cap0;
+    c.popcap = cap_for(V);
+    c.arena0 = (int64_t)nclauses * 2 * cap0;
+    c.step_limit = step_limit;
+    c.clause_limit = clause_limit;
+    c.limit_ticks = time_limit_s > 0 ? (uint64_t)std::max(1.0, time_limit_s * hz) : 0;
+    // inline steps (opt-in); recording reads the clause list after every
+    // step: one step per slot
+    c.inline_steps = !inline_on ? 0 : rec.on() ? 1 : (1 << 30);
+    SATMI_TRY(dp_upload(Wk, c, var2dense, dense2var));
+    DpArgs A = dp_args(Wk, c);
     if (nclauses > 0) {
         hipLaunchKernelGGL(dp_encode_kernel, dim3(grid_for(nclauses)), dim3(256), 0, s, A, nclauses,
                            Wk.d_off.as<int32_t>(), Wk.d_lits.as<int32_t>(), cap0);
         SATMI_HIP(hipGetLastError());
     }
-    // device time of the elimination steps: one event pair per batch
-    size_t nev = 0;
-    const auto next_events = [&]() -> hipEvent_t * {
-        if (2 * nev + 2 > Wk.ev.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return nullptr;
-            Wk.ev.push_back(a);
-            Wk.ev.push_back(b);
-        }
-        return &Wk.ev[2 * nev++];
-    };
-    // one elimination step: DP_LAUNCHES_PER_STEP launches, sizes on the device
-    const auto enqueue_step = [&](const DpArgs &a) -> int {
-        const int gp = (int)std::min<int64_t>(DP_GRID_PAIRS, (a.pair_cap + 255) / 256);
-        const int gc = (int)std::min<int64_t>(DP_GRID_ASM, (a.ncl_cap + ASM_WAVES - 1) / ASM_WAVES);
-        if (a.inline_steps > 0) hipLaunchKernelGGL(dp_pop_split_kernel<true>, dim3(1), dim3(POP_THREADS), 0, s, a);
-        else hipLaunchKernelGGL(dp_pop_split_kernel<false>, dim3(1), dim3(POP_THREADS), 0, s, a);
-        hipLaunchKernelGGL(dp_pairs_kernel, dim3(gp), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(dp_hash_kernel, dim3(gp), dim3(256), 0, s, a);
-        const dim3 gt((unsigned)std::min<int64_t>(DP_GRID_TEST, std::max<int64_t>(64, a.pair_cap / 256)));
-        switch (a.K) {
-            case 2: hipLaunchKernelGGL(dp_remtest_kernel<2>, gt, dim3(TEST_TILE), 0, s, a); break;
-            case 4: hipLaunchKernelGGL(dp_remtest_kernel<4>, gt, dim3(TEST_TILE), 0, s, a); break;
-            case 6: hipLaunchKernelGGL(dp_remtest_kernel<6>, gt, dim3(TEST_TILE), 0, s, a); break;
-            case 8: hipLaunchKernelGGL(dp_remtest_kernel<8>, gt, dim3(TEST_TILE), 0, s, a); break;
-            default: hipLaunchKernelGGL(dp_remtest_kernel<0>, gt, dim3(TEST_TILE), 0, s, a);
-        }
-        hipLaunchKernelGGL(dp_survlist_kernel, dim3(gp), dim3(256), 0, s, a);
-        switch (a.K) {
-            case 2: hipLaunchKernelGGL(dp_survtest_kernel<2>, gt, dim3(TEST_TILE), 0, s, a); break;
-            case 4: hipLaunchKernelGGL(dp_survtest_kernel<4>, gt, dim3(TEST_TILE), 0, s, a); break;
-            case 6: hipLaunchKernelGGL(dp_survtest_kernel<6>, gt, dim3(TEST_TILE), 0, s, a); break;
-            case 8: hipLaunchKernelGGL(dp_survtest_kernel<8>, gt, dim3(TEST_TILE), 0, s, a); break;
-            default: hipLaunchKernelGGL(dp_survtest_kernel<0>, gt, dim3(TEST_TILE), 0, s, a);
-        }
-        hipLaunchKernelGGL(dp_kept_kernel, dim3(1), dim3(POP_THREADS), 0, s, a);
-        hipLaunchKernelGGL(dp_assemble_kernel, dim3(gc), dim3(64 * ASM_WAVES), 0, s, a);
-        SATMI_HIP(hipGetLastError());
-        return SATMI_OK;
-    };
-    int64_t rec_clauses = 0, rec_lits = 0;
-    int recorded_steps = 0;
-    std::vector<int64_t> h_off;
-    std::vector<int32_t> h_mask, h_arena;
-    int enqueued = 0;   // steps enqueued since the last resume
-    bool first_batch = true;
-    for (;;) {
-        // at most V steps eliminate a variable, then one pop finds the set empty;
-        // a slot may run many steps inline, so a call with the arguments of the
-        // last one starts with as many slots as that one used (the next batch,
-        // if any, with the full count)
-        const bool hinted = first_batch && Wk.hint_slots > 0 && std::memcmp(&Wk.hint_args, &A, sizeof(DpArgs)) == 0;
-        const int batch = record ? 1 : hinted ? std::min(Wk.hint_slots, V + 1) : std::min(64, V + 1);
-        first_batch = false;
-        hipEvent_t *ev = next_events();
-        if (!ev) {
-            set_error("satmi_dp_host: hipEventCreate failed");
-            return SATMI_ERR_HIP;
-        }
-        SATMI_HIP(hipEventRecord(ev[0], s));
-        // A batch is ~10 launches per step whose arguments depend only on the
-        // workspace and the call's limits: the second time the same batch is
-        // enqueued it is captured into a HIP graph, and from then on replayed
-        // with one launch (the steps' sizes live on the device either way).
-        DpGraph &G = Wk.graph;
-        const bool same = G.batch == batch && std::memcmp(&G.args, &A, sizeof(DpArgs)) == 0;
-        if (!record && same && G.exec) {
-            SATMI_HIP(hipGraphLaunch(G.exec, s));
-        } else if (!record && same) {
-            hipGraph_t graph = nullptr;
-            SATMI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            int rc = SATMI_OK;
-            for (int k = 0; k < batch && rc == SATMI_OK; ++k) rc = enqueue_step(A);
-            const hipError_t ec = hipStreamEndCapture(s, &graph);
-            if (rc != SATMI_OK || ec != hipSuccess) {
-                if (graph) (void)hipGraphDestroy(graph);
-                G.reset();
-                if (rc != SATMI_OK) return rc;
-                SATMI_HIP(ec);
-            }
-            const hipError_t ei = hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            SATMI_HIP(ei);
-            SATMI_HIP(hipGraphLaunch(G.exec, s));
-        } else {
-            if (!record) {   // remember the batch: captured if it comes again
-                G.reset();
-                G.args = A;
-                G.batch = batch;
-            }
-            for (int k = 0; k < batch; ++k) SATMI_TRY(enqueue_step(A));
-        }
-        SATMI_HIP(hipEventRecord(ev[1], s));
-        enqueued += batch;
-        g_dp_stats.launches += (int64_t)batch * DP_LAUNCHES_PER_STEP;
-        SATMI_HIP(hipMemcpyAsync(Wk.pin, Wk.state.p, sizeof(DpState), hipMemcpyDeviceToHost, s));
-        SATMI_HIP(hipStreamSynchronize(s));
-        if (st.set_ovf) {
-            set_error("satmi_dp_host: set model table overflow");
-            return SATMI_ERR_TOO_LARGE;
-        }
-        if (st.overflow) {   // grow what ran out, then run the step again
-            const int cur = st.cur;
-            for (int b = 0; b < 4; ++b) g_dp_stats.resumes[b] += (st.overflow >> b) & 1;
-            if (st.overflow & OVF_PAIRS) SATMI_TRY(grow_pairs(Wk, st.need[0], K));
-            if (st.overflow & OVF_NCL) SATMI_TRY(grow_ncl(Wk, st.need[1], K, cur, st.ncl));
-            if (st.overflow & OVF_ARENA) {
-                SATMI_TRY(Wk.arena.grow(4 * (size_t)st.need[2], s, &DP_OOM, 4 * (size_t)st.arena_top));
-                Wk.arena_cap = (int64_t)(Wk.arena.cap / 4);
-            }
-            if (st.overflow & OVF_XS) {
-                SATMI_TRY(Wk.xs.grow(4 * (size_t)st.need[3], s, &DP_OOM));
-                Wk.xs_cap = (int64_t)(Wk.xs.cap / 4);
-            }
-            st.overflow = 0;
-            st.done = 0;
-            SATMI_HIP(hipMemcpyAsync(Wk.state.p, Wk.pin, sizeof(DpState), hipMemcpyHostToDevice, s));
-            A = args();
-            SATMI_HIP(hipMemsetAsync(Wk.firstpos.p, 0xFF, 8 * (size_t)V, s));
-            hipLaunchKernelGGL(dp_firstpos_kernel, dim3(grid_for(std::max<int64_t>(st.ncl, 1))), dim3(256), 0, s, A);
-            SATMI_HIP(hipGetLastError());
-            enqueued = 0;
-            continue;
-        }
-        if (record && st.pending && st.steps > recorded_steps && st.steps < rec_step_cap) {
-            // the clause list after this step, each clause in its set iteration order
-            const int64_t n2 = st.ncl2;
-            const int nxt = st.cur ^ 1;
-            h_off.resize((size_t)std::max<int64_t>(n2, 1));
-            h_mask.resize((size_t)std::max<int64_t>(n2, 1));
-            h_arena.resize((size_t)std::max<int64_t>(st.arena_top, 1));
-            if (n2 > 0) {
-                SATMI_HIP(hipMemcpyAsync(h_off.data(), Wk.g[nxt].off.p, 8 * (size_t)n2, hipMemcpyDeviceToHost, s));
-                SATMI_HIP(hipMemcpyAsync(h_mask.data(), Wk.g[nxt].mask.p, 4 * (size_t)n2, hipMemcpyDeviceToHost, s));
-                SATMI_HIP(hipMemcpyAsync(h_arena.data(), Wk.arena.p, 4 * (size_t)st.arena_top, hipMemcpyDeviceToHost,
-                                         s));
-                SATMI_HIP(hipStreamSynchronize(s));
-            }
-            for (int64_t c = 0; c < n2 && rec_clauses + 1 < rec_clause_cap; ++c) {
-                for (int64_t i = 0; i <= h_mask[c]; ++i) {
-                    const int32_t k = h_arena[h_off[c] + i];
-                    if (k != PY_EMPTY && k != PY_DUMMY && rec_lits < rec_lit_cap) h_rec_lits[rec_lits++] = k;
-                }
-                h_rec_clause_off[++rec_clauses] = rec_lits;
-            }
-            h_rec_step_off[st.steps] = rec_clauses;
-            recorded_steps = st.steps;
-        }
-        if (st.done) break;
-        if (enqueued > V + 1) {   // cannot happen: every step eliminates a variable
-            set_error("satmi_dp_host: elimination did not terminate");
-            return SATMI_ERR_HIP;
-        }
-    }
+    SATMI_TRY(dp_eliminate(Wk, c, rec, A));
+    const DpState &st = Wk.st();
     Wk.epoch = st.epoch + 1;
     if (std::getenv("SATMI_DP_PHASES")) {   // diagnostics: dp_pop_split_kernel's phase clocks (ticks of hz)
         std::fprintf(stderr, "dp phases us: pop+split %.1f pairs %.1f dedup %.1f remtest %.1f survtest %.1f "
@@ -2030,7 +2066,7 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
                      st.ph[4] * 1e6 / hz, st.ph[5] * 1e6 / hz, st.ph[6] * 1e6 / hz, st.slots,
                      (long long)st.inl_steps, st.steps);
     }
-    if (!record) {   // the slots this call used: the next call's first batch
+    if (!rec.on()) {   // the slots this call used: the next call's first batch
         Wk.hint_args = A;
         Wk.hint_slots = std::max(1, st.slots);
     }
@@ -2044,10 +2080,7 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
     g_dp_stats.steps = steps;
     g_dp_stats.tests = st.tests;
     g_dp_stats.new_clauses = st.new_total;
-    for (size_t i = 0; i < nev; ++i) {   // the stream has drained
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, Wk.ev[2 * i], Wk.ev[2 * i + 1]) == hipSuccess) g_dp_stats.device_ms += ms;
-    }
+    g_dp_stats.device_ms = Wk.timer.total();   // the stream has drained
     *h_result = st.result;
     *h_steps = steps;
     lease.ok = true;

@@ -2,18 +2,21 @@
 // dpll_scan.hip, dp.hip, resolution.hip, cdcl.hip, resolution_batch.hip,
 // dp_batch.hip): the error-propagating SATMI_TRY, a CU's LDS size, the alignment
 // and carving of layouts, the cached device facts, the grow-only device and
-// pinned buffers, the workspace pool with its lease, the dense variable index,
-// and the DPLL launches' per-stream state (the two batched entry points share
-// batch_keys.h and batch_host.h besides).  Host code only; device helpers are
-// in common.h.
+// pinned buffers, the workspace pool with its lease and the stream a workspace
+// owns, event-pair timing, capture-then-replay of a repeated launch segment,
+// the dense variable index, and the DPLL launches' per-stream state (the two
+// batched entry points share batch_keys.h and batch_host.h besides).  Host
+// code only; device helpers are in common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -170,7 +173,21 @@ struct PinBuf {
 // it when done, so concurrent calls from any number of host threads each own
 // one and the number of workspaces is the peak number of concurrent calls.
 // W has `int dev`, `hipStream_t stream` and `bool open()` (creates the stream
-// and whatever else a fresh workspace needs).
+// and whatever else a fresh workspace needs): it derives from WorkStream.
+struct WorkStream {
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    WorkStream() = default;
+    WorkStream(const WorkStream &) = delete;
+    WorkStream &operator=(const WorkStream &) = delete;
+    // a base's destructor runs after the members of the workspace went: its
+    // graph, events and buffers are gone before their stream
+    ~WorkStream() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    bool open() { return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess; }
+};
+
 template <class W>
 struct Pool {
     static Pool &get() {
@@ -229,6 +246,101 @@ struct Lease {
         if (!w) return;
         if (ok) Pool<W>::get().release(w);
         else Pool<W>::destroy(w);
+    }
+};
+
+// ---------------------------------------------------------------- event-pair timing
+// Times launches on one stream: begin() / end() bracket them, total() sums.
+// The pairs are kept between calls (reset() starts a call's count afresh); a
+// failure is SATMI_ERR_HIP under the caller's name `who`.
+struct EventTimer {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+    size_t used = 0;
+    EventTimer() = default;
+    EventTimer(const EventTimer &) = delete;
+    EventTimer &operator=(const EventTimer &) = delete;
+    ~EventTimer() {
+        for (auto &e : ev) {
+            (void)hipEventDestroy(e.first);
+            (void)hipEventDestroy(e.second);
+        }
+    }
+    int begin(hipStream_t s, const char *who) {
+        if (used == ev.size()) {
+            hipEvent_t a = nullptr, b = nullptr;
+            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+                if (a) (void)hipEventDestroy(a);
+                set_error(std::string(who) + ": hipEventCreate failed");
+                return SATMI_ERR_HIP;
+            }
+            ev.push_back({a, b});
+        }
+        return record(ev[used].first, s, who);
+    }
+    int end(hipStream_t s, const char *who) { return record(ev[used++].second, s, who); }
+    void reset() { used = 0; }
+    double total() const {   // after the stream drained
+        double ms = 0.0;
+        for (size_t i = 0; i < used; ++i) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, ev[i].first, ev[i].second) == hipSuccess) ms += t;
+        }
+        return ms;
+    }
+
+private:
+    static int record(hipEvent_t e, hipStream_t s, const char *who) {
+        const hipError_t rc = hipEventRecord(e, s);
+        return rc == hipSuccess ? SATMI_OK : hip_fail(rc, (std::string(who) + ": hipEventRecord").c_str());
+    }
+};
+
+// ---------------------------------------------------------------- graph replay
+// A segment of launches that a workspace enqueues again and again with the
+// same arguments: the first time it is enqueued plainly and its key (the bytes
+// of everything its launches read from the host: build it as a zero-initialised
+// struct, so padding compares equal) is remembered; the second time the same
+// key comes it is captured into a HIP graph, and from then on replayed with one
+// launch.  `enqueue` puts the segment on the stream and returns a SATMI_* code.
+struct ReplayGraph {
+    hipGraphExec_t exec = nullptr;
+    std::vector<unsigned char> key;
+    ReplayGraph() = default;
+    ReplayGraph(const ReplayGraph &) = delete;
+    ReplayGraph &operator=(const ReplayGraph &) = delete;
+    ~ReplayGraph() { reset(); }
+    void reset() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        exec = nullptr;
+        key.clear();
+    }
+    template <class Key, class F>
+    int run(hipStream_t s, const Key &k, F &&enqueue) {
+        static_assert(std::is_trivially_copyable<Key>::value, "a key is compared as bytes");
+        const bool same = key.size() == sizeof(Key) && std::memcmp(key.data(), &k, sizeof(Key)) == 0;
+        if (same && exec) {
+            SATMI_HIP(hipGraphLaunch(exec, s));
+        } else if (same) {
+            hipGraph_t graph = nullptr;
+            SATMI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            const int rc = enqueue();
+            const hipError_t ec = hipStreamEndCapture(s, &graph);
+            if (rc != SATMI_OK || ec != hipSuccess) {
+                if (graph) (void)hipGraphDestroy(graph);
+                reset();
+                if (rc != SATMI_OK) return rc;
+                SATMI_HIP(ec);
+            }
+            const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            SATMI_HIP(ei);
+            SATMI_HIP(hipGraphLaunch(exec, s));
+        } else {   // remember the segment: captured if it comes again
+            reset();
+            key.assign((const unsigned char *)&k, (const unsigned char *)&k + sizeof(Key));
+            return enqueue();
+        }
+        return SATMI_OK;
     }
 };
 

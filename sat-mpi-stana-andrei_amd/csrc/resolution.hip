@@ -246,39 +246,6 @@ __global__ void ht_cand_kernel(uint64_t *table, uint64_t mask, KeySrc S, int64_t
     }
 }
 
-// Packed table (at most 31 variables): a key (P, N) is one word P | N << 32 and
-// the table holds the keys themselves, so a probe compares in register -- no
-// second random read of the occupant's key -- and nothing is re-pointed at
-// append time.  Bit 31 of P and N is never set, so no key equals HT_EMPTY.
-__device__ __forceinline__ uint64_t pack_key(const uint64_t *x) { return x[0] | (x[1] << 32); }
-
-// 1 if key k claimed a slot (absent before), 0 if it was present
-__device__ __forceinline__ int ht_insert_packed(uint64_t *table, uint64_t mask, uint64_t k) {
-    uint64_t s = mix64(k) & mask;
-    for (;;) {
-        uint64_t cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == HT_EMPTY) {
-            cur = atomicCAS((unsigned long long *)(table + s), (unsigned long long)HT_EMPTY, (unsigned long long)k);
-            if (cur == HT_EMPTY) return 1;
-        }
-        if (cur == k) return 0;
-        s = (s + 1) & mask;
-    }
-}
-
-__global__ void ht_clauses_packed_kernel(uint64_t *table, uint64_t mask, const uint64_t *clauses, int64_t c0,
-                                         int64_t c1) {
-    for (int64_t c = c0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < c1; c += (int64_t)gridDim.x * blockDim.x)
-        (void)ht_insert_packed(table, mask, pack_key(clauses + 2 * c));
-}
-
-__global__ void ht_cand_packed_kernel(uint64_t *table, uint64_t mask, const uint64_t *cand, int64_t n,
-                                      int64_t *flag) {
-    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
-        flag[t] = ht_insert_packed(table, mask, pack_key(cand + 2 * t));
-    }
-}
-
 // clauses.extend(new): the claimed candidates become clauses first .. first +
 // count, in append order; their table entries are re-pointed at the clause
 // array (the candidate buffer is reused by the next chunk)
@@ -743,70 +710,19 @@ struct ResRegrow {
 };
 thread_local ResRegrow g_regrow;
 
-// Times launches on one stream: begin() / end() bracket them, total() sums.
-struct EventTimer {
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
-    size_t used = 0;
-    ~EventTimer() {
-        for (auto &e : ev) {
-            (void)hipEventDestroy(e.first);
-            (void)hipEventDestroy(e.second);
-        }
-    }
-    hipEvent_t begin(hipStream_t s) {
-        if (used == ev.size()) {
-            hipEvent_t a = nullptr, b = nullptr;
-            if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return nullptr;
-            ev.push_back({a, b});
-        }
-        (void)hipEventRecord(ev[used].first, s);
-        return ev[used].first;
-    }
-    void end(hipStream_t s) { (void)hipEventRecord(ev[used++].second, s); }
-    void reset() { used = 0; }
-    double total() {   // after the stream drained
-        double ms = 0.0;
-        for (size_t i = 0; i < used; ++i) {
-            float t = 0.0f;
-            if (hipEventElapsedTime(&t, ev[i].first, ev[i].second) == hipSuccess) ms += t;
-        }
-        return ms;
-    }
-};
-
 // Device buffers of satmi_resolution_host, kept between calls (grow-only) in
 // the workspace pool (host.h): concurrent calls overlap on the device, each on
 // its own non-blocking stream.  A saturation of a small formula is a few
 // passes of small launches, so allocating its buffers per call cost more than
 // its kernels.  A call that failed part-way destroys its workspace: its table
 // may hold stale keys.
-// The packed path's first segment of a call (state init, key packing, table
-// seeding, the first batch of passes, the state's copy back), captured into a
-// HIP graph the second time the same segment is enqueued and replayed from
-// then on: one launch instead of ~16 host submissions, whose gaps were a
-// quarter of a php-res call.  Keyed by everything its launches read from the
-// host.
-struct ResGraph {
-    hipGraphExec_t exec = nullptr;
-    ResArgs args;
-    int64_t ncl = -1;
-    uint64_t tslots = 0;
-    int batch = 0;
-    const void *down = nullptr;     // non-null: the segment copies the per-pass counts back too
-    const void *pstate = nullptr;   // the pinned buffer the segment copies into
-    ResGraph() { std::memset(&args, 0, sizeof(args)); }
-    void reset() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        exec = nullptr;
-        ncl = -1;
-    }
-};
-
-struct ResWork {
+struct ResWork : WorkStream {
     DevBuf clauses, cand, counters, table, flag, pos, slotv, tiles, grand;
     DevBuf keys, state, stage, stripes;            // the packed path (state: ResState, then the per-pass counts)
     DevBuf up;                                     // the call's inputs (one copy from up_h)
     PinBuf up_h, pstate;                           // pinned staging: inputs; the state and counts back
+    PinBuf pin;   // pinned host words (coherent): the general path's counters and claim count; words()[7]: the
+                  // packed path's batch flag (res_copyout_kernel)
     struct Clean {   // the buffers the last reset (packed path) left clean; all null: not clean
         const void *table = nullptr, *state = nullptr, *stripes = nullptr;
         int64_t slot_base = -1;
@@ -816,57 +732,83 @@ struct ResWork {
         }
     } clean;
     EventTimer t_pairs, t_claims;
-    hipStream_t stream = nullptr;
-    unsigned long long *pin = nullptr;   // pinned host words (coherent): the general path's counters and claim
-                                         // count; pin[7]: the packed path's batch flag (res_copyout_kernel)
-    int dev = 0;
-    ResGraph graph;
-    ~ResWork() {   // only a workspace that failed part-way is destroyed (after its stream drained)
-        graph.reset();
-        if (stream) (void)hipStreamDestroy(stream);
-        if (pin) (void)hipHostFree(pin);
-    }
-    bool open() {
-        return hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess &&
-               hipHostMalloc((void **)&pin, 64, hipHostMallocCoherent) == hipSuccess;
-    }
+    ReplayGraph graph;   // the packed path's first segment of a call (see ResGraphKey)
+    bool open() { return WorkStream::open() && pin.reserve(64, hipHostMallocCoherent) == SATMI_OK; }
+    unsigned long long *words() const { return (unsigned long long *)pin.p; }
 };
 
-// decode a pass's new keys (packed or bitset words) into sorted literal lists
-void record_pass(const std::vector<uint64_t> &hkeys, int64_t nnew, bool packed, int W, int V,
-                 const std::vector<int32_t> &dense2var, int passes, int32_t *h_rec_lits, int64_t rec_lit_cap,
-                 int64_t *h_rec_clause_off, int64_t rec_clause_cap, int64_t *h_rec_pass_off, int64_t &rec_clauses,
-                 int64_t &rec_lits) {
+// The packed path's first segment of a call (state init, key packing, table
+// seeding, the first batch of passes, the state's copy back) is captured into a
+// HIP graph the second time the same segment is enqueued and replayed from
+// then on (host.h's ReplayGraph): one launch instead of ~16 host submissions,
+// whose gaps were a quarter of a php-res call.  Its key: everything its
+// launches read from the host.
+struct ResGraphKey {
+    ResArgs args;
+    int64_t ncl;
+    uint64_t tslots;
+    int batch;
+    const void *down;     // non-null: the segment copies the per-pass counts back too
+    const void *pstate;   // the pinned buffer the segment copies into
+};
+
+// A call of satmi_resolution_host, filled once: the formula as uploaded, the
+// caller's limits, outputs and recording arrays, and how far those are filled.
+struct ResCall {
+    int nclauses;
+    size_t o_lits, o_map;   // in ResWork::up, after the clause offsets: the literals, the variable map
+    int V, W;
+    const std::vector<int32_t> *dense2var;
+    int64_t max_passes, clause_limit;
+    double time_limit_s;
+    int64_t slot_base;
+    int32_t *result, *passes;
+    int64_t *pass_new;
+    int pass_cap;
+    int32_t *rec_lits;
+    int64_t rec_lit_cap;
+    int64_t *rec_clause_off;
+    int64_t rec_clause_cap;
+    int64_t *rec_pass_off;
+    int rec_pass_cap;
+    int64_t rec_clauses = 0, rec_nlits = 0;
+    bool record() const { return rec_lits && rec_clause_off && rec_pass_off; }
+};
+
+// decode the new keys of pass `pass` (packed or bitset words) into sorted
+// literal lists; whole clauses, stopping at the first that does not fit
+void record_pass(ResCall &c, const std::vector<uint64_t> &hkeys, int64_t nnew, bool packed, int pass) {
+    const int W = c.W;
+    const std::vector<int32_t> &dense2var = *c.dense2var;
     // each clause as ascending literals, the clauses in ascending order
     // (deterministic whatever the append order)
-    std::vector<std::vector<int32_t>> pass((size_t)nnew);
-    for (int64_t c = 0; c < nnew; ++c) {
-        for (int d = 0; d < V; ++d) {
+    std::vector<std::vector<int32_t>> cls((size_t)nnew);
+    for (int64_t i = 0; i < nnew; ++i) {
+        for (int d = 0; d < c.V; ++d) {
             bool pos, neg;
             if (packed) {
-                const uint64_t k = hkeys[(size_t)c];
+                const uint64_t k = hkeys[(size_t)i];
                 pos = (k >> d) & 1ull;
                 neg = (k >> (32 + d)) & 1ull;
             } else {
-                const uint64_t *k = hkeys.data() + c * 2 * W;
+                const uint64_t *k = hkeys.data() + i * 2 * W;
                 pos = (k[d >> 6] >> (d & 63)) & 1ull;
                 neg = (k[W + (d >> 6)] >> (d & 63)) & 1ull;
             }
-            if (pos) pass[(size_t)c].push_back(dense2var[(size_t)d]);
-            if (neg) pass[(size_t)c].push_back(-dense2var[(size_t)d]);
+            if (pos) cls[(size_t)i].push_back(dense2var[(size_t)d]);
+            if (neg) cls[(size_t)i].push_back(-dense2var[(size_t)d]);
         }
-        std::sort(pass[(size_t)c].begin(), pass[(size_t)c].end());
+        std::sort(cls[(size_t)i].begin(), cls[(size_t)i].end());
     }
-    std::sort(pass.begin(), pass.end());
-    for (const auto &cl : pass) {
-        if (rec_clauses + 1 >= rec_clause_cap || rec_lits + (int64_t)cl.size() > rec_lit_cap) break;
-        std::copy(cl.begin(), cl.end(), h_rec_lits + rec_lits);
-        rec_lits += (int64_t)cl.size();
-        h_rec_clause_off[++rec_clauses] = rec_lits;
+    std::sort(cls.begin(), cls.end());
+    for (const auto &cl : cls) {
+        if (c.rec_clauses + 1 >= c.rec_clause_cap || c.rec_nlits + (int64_t)cl.size() > c.rec_lit_cap) break;
+        std::copy(cl.begin(), cl.end(), c.rec_lits + c.rec_nlits);
+        c.rec_nlits += (int64_t)cl.size();
+        c.rec_clause_off[++c.rec_clauses] = c.rec_nlits;
     }
-    h_rec_pass_off[passes + 1] = rec_clauses;
+    c.rec_pass_off[pass + 1] = c.rec_clauses;
 }
-
 
 // grow the packed key buffer to >= want keys, keeping keys [0, keep)
 int grow_keys(ResWork &wk, int64_t want, int64_t keep, hipStream_t s) {
@@ -882,15 +824,14 @@ int grow_keys(ResWork &wk, int64_t want, int64_t keep, hipStream_t s) {
 // the table the previous call's reset left empty), the passes with the state
 // and per-pass counts back in one copy -- replayed from a HIP graph when the
 // same call repeats -- and, not waited for, the reset for the next call.
-int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t o_lits, size_t o_map,
-                      int64_t max_passes, int64_t clause_limit, double time_limit_s,
-                      int64_t slot_base, int V, const std::vector<int32_t> &dense2var, int32_t *h_result,
-                      int32_t *h_passes, int64_t *h_pass_new, int pass_cap, int32_t *h_rec_lits,
-                      int64_t rec_lit_cap, int64_t *h_rec_clause_off, int64_t rec_clause_cap, int64_t *h_rec_pass_off,
-                      int rec_pass_cap) {
+int resolution_packed(ResWork &wk, ResCall &c) {
     hipStream_t s = wk.stream;
+    const int nclauses = c.nclauses;
+    const int64_t max_passes = c.max_passes, slot_base = c.slot_base;
+    const double time_limit_s = c.time_limit_s;
+    const unsigned char *up = wk.up.as<unsigned char>();
     const auto t_call = std::chrono::steady_clock::now();
-    const int PCAP = std::max(1, std::min(pass_cap, 1 << 16));   // passes whose counts the device keeps
+    const int PCAP = std::max(1, std::min(c.pass_cap, 1 << 16));   // passes whose counts the device keeps
     // the state and the per-pass counts in one buffer (one copy back per batch)
     const size_t SOFF = (sizeof(ResState) + 255) & ~(size_t)255;
     SATMI_TRY(wk.keys.reserve(8 * (size_t)std::max<int64_t>(4 * (int64_t)nclauses, 1 << 14), &RES_OOM));
@@ -939,7 +880,7 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
     };
     // keys, table seed, clause count and the deadline's start (t0): one launch
     hipLaunchKernelGGL(res_prologue_kernel, dim3(grid_for(std::max(nclauses, 1))), dim3(256), 0, s, nclauses,
-                       (const int32_t *)up, (const int32_t *)(up + o_lits), (const int32_t *)(up + o_map),
+                       (const int32_t *)up, (const int32_t *)(up + c.o_lits), (const int32_t *)(up + c.o_map),
                        wk.keys.as<uint64_t>(), wk.table.as<uint64_t>(), tslots / RES_BUCKET - 1,
                        wk.state.as<ResState>());
     SATMI_HIP(hipGetLastError());
@@ -957,7 +898,7 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
         A.pass_new = (int64_t *)(wk.state.as<unsigned char>() + SOFF);
         A.pass_cap = PCAP;
         A.max_passes = max_passes;
-        A.clause_limit = clause_limit;
+        A.clause_limit = c.clause_limit;
         A.limit_ticks = time_limit_s > 0 ? (uint64_t)std::max(1.0, time_limit_s * hz) : 0;
         A.slot_base = slot_base;
         A.stage = wk.stage.as<uint64_t>();
@@ -967,21 +908,20 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
     args();
     g_stats = ResStats{};
     g_regrow = ResRegrow{};
-    const bool record = h_rec_lits && h_rec_clause_off && h_rec_pass_off;
-    int64_t rec_clauses = 0, rec_lits = 0;
+    const bool record = c.record();
     std::vector<uint64_t> hkeys;
     const dim3 pass_grid(256, 32);   // j-tiles x i-tiles, grid-stride
     // A batch of passes, then the state and counts back into pinned memory
     // with a flag the host spins on, then the next call's reset if the batch
     // ended the saturation (S->done -- set by an overflow too, whose regrowth
     // re-uploads the state and re-seeds the table)
-    volatile uint32_t *flag = (volatile uint32_t *)(wk.pin + 7);
+    volatile uint32_t *flag = (volatile uint32_t *)(wk.words() + 7);
     const auto passes = [&](int batch) -> int {
         for (int b = 0; b < batch; ++b) {
             hipLaunchKernelGGL(res_pass_packed_kernel, pass_grid, dim3(256), 0, s, A);
             hipLaunchKernelGGL(res_gather_kernel, dim3(2, RES_STRIPES), dim3(256), 0, s, A);
         }
-        const int64_t ncopy = h_pass_new ? std::min<int64_t>(PCAP, st.passes + batch) : 0;
+        const int64_t ncopy = c.pass_new ? std::min<int64_t>(PCAP, st.passes + batch) : 0;
         hipLaunchKernelGGL(res_copyout_kernel, dim3(1), dim3(64), 0, s, wk.state.as<unsigned char>(),
                            (uint32_t)(SOFF + 8 * (size_t)ncopy), wk.pstate.p, (uint32_t *)flag,
                            wk.stripes.as<unsigned long long>());
@@ -1016,37 +956,15 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
         std::atomic_thread_fence(std::memory_order_release);
         if (first) {   // the first batch: replayed from the graph when it repeats
             first = false;
-            ResGraph &G = wk.graph;
-            const void *down = h_pass_new ? (const void *)wk.pstate.p : nullptr;
-            const bool same = G.ncl == nclauses && G.tslots == tslots && G.batch == batch && G.down == down &&
-                              G.pstate == wk.pstate.p && std::memcmp(&G.args, &A, sizeof(ResArgs)) == 0;
-            if (same && G.exec) {
-                SATMI_HIP(hipGraphLaunch(G.exec, s));
-            } else if (same) {
-                hipGraph_t graph = nullptr;
-                SATMI_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-                const int rc = passes(batch);
-                const hipError_t ec = hipStreamEndCapture(s, &graph);
-                if (rc != SATMI_OK || ec != hipSuccess) {
-                    if (graph) (void)hipGraphDestroy(graph);
-                    G.reset();
-                    if (rc != SATMI_OK) return rc;
-                    SATMI_HIP(ec);
-                }
-                const hipError_t ei = hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0);
-                (void)hipGraphDestroy(graph);
-                SATMI_HIP(ei);
-                SATMI_HIP(hipGraphLaunch(G.exec, s));
-            } else {   // remember the segment: captured if it comes again
-                G.reset();
-                G.args = A;
-                G.ncl = nclauses;
-                G.tslots = tslots;
-                G.batch = batch;
-                G.down = down;
-                G.pstate = wk.pstate.p;
-                SATMI_TRY(passes(batch));
-            }
+            ResGraphKey key;
+            std::memset(&key, 0, sizeof(key));
+            key.args = A;
+            key.ncl = nclauses;
+            key.tslots = tslots;
+            key.batch = batch;
+            key.down = c.pass_new ? (const void *)wk.pstate.p : nullptr;
+            key.pstate = wk.pstate.p;
+            SATMI_TRY(wk.graph.run(s, key, [&]() { return passes(batch); }));
         } else {
             SATMI_TRY(passes(batch));
         }
@@ -1086,22 +1004,21 @@ int resolution_packed(ResWork &wk, int nclauses, const unsigned char *up, size_t
             SATMI_TRY(seed(st.ncl));   // (after the state: a seed overflow flag must survive)
             continue;
         }
-        if (record && st.passes > 0 && st.ncl > ncl_before && st.passes < rec_pass_cap) {
+        if (record && st.passes > 0 && st.ncl > ncl_before && st.passes < c.rec_pass_cap) {
             const int64_t nnew = st.ncl - ncl_before;   // batch == 1: this pass's additions
             hkeys.resize((size_t)nnew);
             SATMI_HIP(hipMemcpyAsync(hkeys.data(), wk.keys.as<uint64_t>() + ncl_before, 8 * (size_t)nnew,
                                      hipMemcpyDeviceToHost, s));
             SATMI_HIP(hipStreamSynchronize(s));
-            record_pass(hkeys, nnew, true, 1, V, dense2var, (int)st.passes - 1, h_rec_lits, rec_lit_cap,
-                        h_rec_clause_off, rec_clause_cap, h_rec_pass_off, rec_clauses, rec_lits);
+            record_pass(c, hkeys, nnew, true, (int)st.passes - 1);
         }
         if (st.done) break;
     }
     // the counts came back with the last batch's state (the stream has drained)
-    const int np = (int)std::min<int64_t>(st.passes, std::min(pass_cap, PCAP));
-    if (h_pass_new && np > 0) std::memcpy(h_pass_new, pst_counts, 8 * (size_t)np);
-    *h_result = st.result;
-    *h_passes = (int32_t)st.passes;
+    const int np = (int)std::min<int64_t>(st.passes, std::min(c.pass_cap, PCAP));
+    if (c.pass_new && np > 0) std::memcpy(c.pass_new, pst_counts, 8 * (size_t)np);
+    *c.result = st.result;
+    *c.passes = (int32_t)st.passes;
     g_stats.pairs = st.pairs;
     g_stats.candidates = st.candidates;
     g_stats.pair_ms = (double)st.pass_ticks / hz * 1e3;   // device clock, pass kernels only
@@ -1192,7 +1109,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     const int V = (int)dense2var.size();
     const int W = std::max(1, (V + 63) / 64);
     const int K = 2 * W;
-    const bool packed = V <= 31;   // the packed table (see pack_key) and the fused pass
+    const bool packed = V <= 31;   // a key fits one word P | N << 32: the fused pass (resolution_packed)
     const int64_t slot_base = g_slot_base;
     int dev_id = 0;
     SATMI_HIP(hipGetDevice(&dev_id));
@@ -1228,11 +1145,12 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             SATMI_HIP(hipGetLastError());
         }
     }
+    ResCall call{nclauses,   o_lits,       o_map,        V,         W,
+                 &dense2var, max_passes,   clause_limit, time_limit_s, slot_base,
+                 h_result,   h_passes,     h_pass_new,   pass_cap,
+                 h_rec_lits, rec_lit_cap,  h_rec_clause_off, rec_clause_cap, h_rec_pass_off, rec_pass_cap};
     if (packed) {
-        const int rc = resolution_packed(*wk, nclauses, (const unsigned char *)wk->up.p, o_lits, o_map, max_passes,
-                                         clause_limit, time_limit_s, slot_base, V,
-                                         dense2var, h_result, h_passes, h_pass_new, pass_cap, h_rec_lits,
-                                         rec_lit_cap, h_rec_clause_off, rec_clause_cap, h_rec_pass_off, rec_pass_cap);
+        const int rc = resolution_packed(*wk, call);
         if (rc == SATMI_OK) lease.ok = true;
         return rc;
     }
@@ -1255,38 +1173,25 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
         tcap = table_slots(room);
         SATMI_TRY(table.reserve(8 * tcap, &RES_OOM));
         SATMI_HIP(hipMemsetAsync(table.p, 0xFF, 8 * tcap, s));   // HT_EMPTY
-        if (nkeys > 0 && packed)
-            hipLaunchKernelGGL(ht_clauses_packed_kernel, dim3(grid_for(nkeys)), dim3(PRIM_BLOCK), 0, s,
-                               table.as<uint64_t>(), tcap - 1, clauses.as<uint64_t>(), (int64_t)0, nkeys);
-        else if (nkeys > 0)
+        if (nkeys > 0)
             hipLaunchKernelGGL(ht_clauses_kernel, dim3(grid_for(nkeys)), dim3(PRIM_BLOCK), 0, s, table.as<uint64_t>(),
                                tcap - 1, KeySrc{clauses.as<uint64_t>(), nullptr, 0, K}, (int64_t)0, nkeys);
         SATMI_HIP(hipGetLastError());
         return SATMI_OK;
     };
     const auto launch_pairs = [&](int64_t j0, int64_t j1, int64_t cap) {
-        const int grid = (int)std::min<int64_t>(j1 - j0, 65536);
-        switch (W) {
-            case 1:
-                hipLaunchKernelGGL(res_pairs_kernel<1>, dim3(grid), dim3(256), 0, s, clauses.as<uint64_t>(), W, j0, j1,
-                                   d_count, d_empty, cand.as<uint64_t>(), cap, slot_base);
-                break;
-            case 2:
-                hipLaunchKernelGGL(res_pairs_kernel<2>, dim3(grid), dim3(256), 0, s, clauses.as<uint64_t>(), W, j0, j1,
-                                   d_count, d_empty, cand.as<uint64_t>(), cap, slot_base);
-                break;
-            case 3:
-                hipLaunchKernelGGL(res_pairs_kernel<3>, dim3(grid), dim3(256), 0, s, clauses.as<uint64_t>(), W, j0, j1,
-                                   d_count, d_empty, cand.as<uint64_t>(), cap, slot_base);
-                break;
-            case 4:
-                hipLaunchKernelGGL(res_pairs_kernel<4>, dim3(grid), dim3(256), 0, s, clauses.as<uint64_t>(), W, j0, j1,
-                                   d_count, d_empty, cand.as<uint64_t>(), cap, slot_base);
-                break;
-            default:
-                hipLaunchKernelGGL(res_pairs_kernel<0>, dim3(grid), dim3(256), 0, s, clauses.as<uint64_t>(), W, j0, j1,
-                                   d_count, d_empty, cand.as<uint64_t>(), cap, slot_base);
-        }
+        const dim3 g((unsigned)std::min<int64_t>(j1 - j0, 65536)), b(256);
+        // the arguments stand once; an instance per line (tests/res_paths.py reads the widths off these)
+        const auto dispatch = [&](auto... a) {
+            switch (W) {
+                case 1: hipLaunchKernelGGL(res_pairs_kernel<1>, g, b, 0, s, a...); break;
+                case 2: hipLaunchKernelGGL(res_pairs_kernel<2>, g, b, 0, s, a...); break;
+                case 3: hipLaunchKernelGGL(res_pairs_kernel<3>, g, b, 0, s, a...); break;
+                case 4: hipLaunchKernelGGL(res_pairs_kernel<4>, g, b, 0, s, a...); break;
+                default: hipLaunchKernelGGL(res_pairs_kernel<0>, g, b, 0, s, a...);
+            }
+        };
+        dispatch(clauses.as<uint64_t>(), W, j0, j1, d_count, d_empty, cand.as<uint64_t>(), cap, slot_base);
     };
     const auto grow_clauses = [&](int64_t want) {
         if ((size_t)want * K * 8 <= clauses.cap) return SATMI_OK;
@@ -1294,7 +1199,7 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
         return clauses.move_to(8 * (size_t)want * K * 2, s, &RES_OOM, clauses.cap);   // twice the room, every clause kept
     };
 
-    int64_t jlo = 0, rec_clauses = 0, rec_lits = 0;
+    int64_t jlo = 0;
     int passes = 0;
     bool stopped = false;   // a limit (deadline) ended a pass early
     std::vector<uint64_t> hkeys;
@@ -1326,15 +1231,15 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             for (int attempt = 0;; ++attempt) {
                 const int64_t cap = (int64_t)(cand.cap / (8 * (size_t)K));
                 hc = {(unsigned long long)slot_base, 0, 0};
-                std::memcpy(wk->pin, &hc, 16);   // staged in pinned memory: a truly asynchronous copy
-                SATMI_HIP(hipMemcpyAsync(counters.p, wk->pin, 16, hipMemcpyHostToDevice, s));
-                t_pairs.begin(s);
+                std::memcpy(wk->pin.p, &hc, 16);   // staged in pinned memory: a truly asynchronous copy
+                SATMI_HIP(hipMemcpyAsync(counters.p, wk->pin.p, 16, hipMemcpyHostToDevice, s));
+                SATMI_TRY(t_pairs.begin(s, "satmi_resolution_host"));
                 launch_pairs(j0, j1, cap);
-                t_pairs.end(s);
+                SATMI_TRY(t_pairs.end(s, "satmi_resolution_host"));
                 SATMI_HIP(hipGetLastError());
-                SATMI_HIP(hipMemcpyAsync(wk->pin, counters.p, 16, hipMemcpyDeviceToHost, s));
+                SATMI_HIP(hipMemcpyAsync(wk->pin.p, counters.p, 16, hipMemcpyDeviceToHost, s));
                 SATMI_HIP(hipStreamSynchronize(s));
-                std::memcpy(&hc, wk->pin, 16);
+                std::memcpy(&hc, wk->pin.p, 16);
                 const int64_t counted = (int64_t)(hc.count - (unsigned long long)slot_base);
                 if (hc.empty || counted <= cap) break;
                 if (attempt > 0) {   // cannot happen: the re-run had room for every counted candidate
@@ -1362,28 +1267,24 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             SATMI_TRY(slotv.reserve(8 * (size_t)nc, &RES_OOM));
             SATMI_TRY(tiles.reserve(8 * (size_t)((nc + SCAN_TILE - 1) / SCAN_TILE + 1), &RES_OOM));
             SATMI_TRY(grand.reserve(8, &RES_OOM));
-            t_claims.begin(s);
-            if (packed)
-                hipLaunchKernelGGL(ht_cand_packed_kernel, dim3(grid_for(nc)), dim3(PRIM_BLOCK), 0, s,
-                                   table.as<uint64_t>(), tcap - 1, cand.as<uint64_t>(), nc, flag.as<int64_t>());
-            else
-                hipLaunchKernelGGL(ht_cand_kernel, dim3(grid_for(nc)), dim3(PRIM_BLOCK), 0, s, table.as<uint64_t>(),
-                                   tcap - 1, KeySrc{clauses.as<uint64_t>(), cand.as<uint64_t>(), slot_base, K}, nc,
-                                   flag.as<int64_t>(), slotv.as<int64_t>());
-            t_claims.end(s);
+            SATMI_TRY(t_claims.begin(s, "satmi_resolution_host"));
+            hipLaunchKernelGGL(ht_cand_kernel, dim3(grid_for(nc)), dim3(PRIM_BLOCK), 0, s, table.as<uint64_t>(),
+                               tcap - 1, KeySrc{clauses.as<uint64_t>(), cand.as<uint64_t>(), slot_base, K}, nc,
+                               flag.as<int64_t>(), slotv.as<int64_t>());
+            SATMI_TRY(t_claims.end(s, "satmi_resolution_host"));
             g_stats.candidates += nc;
             SATMI_HIP(hipGetLastError());
             SATMI_TRY(exclusive_scan(flag.as<int64_t>(), pos.as<int64_t>(), nc, tiles.as<int64_t>(),
                                      grand.as<int64_t>(), s));
             int64_t nwin = 0;
-            SATMI_HIP(hipMemcpyAsync(wk->pin + 2, grand.p, 8, hipMemcpyDeviceToHost, s));
+            SATMI_HIP(hipMemcpyAsync(wk->words() + 2, grand.p, 8, hipMemcpyDeviceToHost, s));
             SATMI_HIP(hipStreamSynchronize(s));
-            nwin = (int64_t)wk->pin[2];
+            nwin = (int64_t)wk->words()[2];
             if (nwin == 0) continue;
             SATMI_TRY(grow_clauses(ncl + nnew + nwin));
             hipLaunchKernelGGL(res_append_kernel, dim3(grid_for(nc)), dim3(PRIM_BLOCK), 0, s, cand.as<uint64_t>(),
                                flag.as<int64_t>(), pos.as<int64_t>(), slotv.as<int64_t>(), nc, K,
-                               clauses.as<uint64_t>(), ncl + nnew, packed ? nullptr : table.as<uint64_t>());
+                               clauses.as<uint64_t>(), ncl + nnew, table.as<uint64_t>());
             SATMI_HIP(hipGetLastError());
             nnew += nwin;
         }
@@ -1397,13 +1298,12 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
             break;
         }
         if (h_pass_new && passes < pass_cap) h_pass_new[passes] = nnew;
-        if (h_rec_lits && h_rec_clause_off && h_rec_pass_off && passes + 1 < rec_pass_cap) {
+        if (call.record() && passes + 1 < rec_pass_cap) {
             hkeys.resize((size_t)nnew * K);
             SATMI_HIP(hipMemcpyAsync(hkeys.data(), clauses.as<uint64_t>() + ncl * K, 8 * (size_t)nnew * K,
                                      hipMemcpyDeviceToHost, s));
             SATMI_HIP(hipStreamSynchronize(s));
-            record_pass(hkeys, nnew, false, W, V, dense2var, passes, h_rec_lits, rec_lit_cap, h_rec_clause_off,
-                        rec_clause_cap, h_rec_pass_off, rec_clauses, rec_lits);
+            record_pass(call, hkeys, nnew, false, passes);
         }
         ++passes;
         jlo = ncl;

@@ -134,6 +134,33 @@ def test_concurrent_solves_from_threads():
         assert (r["result"], r["vars"]) == (o["result"], o["vars"]) and r["clauses"] == o["clauses"][:_completed(o)]
 
 
+def test_graph_replay_alternating_formulas_of_one_shape():
+    """The captured step batch is keyed by the argument bytes and the batch
+    size, not by the clauses.  Two different random 3-SAT formulas over the same
+    12 variables (30 clauses each, so V, K and the DpArgs bytes agree), solved
+    alternately and unrecorded so the batch is enqueued, captured and then
+    replayed for both: every call gives its own formula's verdict, step count
+    and eliminated variables (a replay reads the newly encoded clauses).  Seed 3
+    is satisfiable after 11 steps (12 step slots: the last pop finds no
+    variable), seed 519 unsatisfiable in its 12th (12 slots), so the learned
+    batch size is the same and a stale replay cannot pass."""
+    def formula(seed, nv=12, m=30):
+        rng = random.Random(seed)
+        while True:
+            f = [[v if rng.random() < 0.5 else -v for v in rng.sample(range(1, nv + 1), 3)] for _ in range(m)]
+            if len({abs(l) for c in f for l in c}) == nv:
+                return f
+
+    fs = [formula(3), formula(519)]
+    want = [oracle.dp(f) for f in fs]
+    assert fs[0] != fs[1] and all(o["steps"] >= 3 for o in want)
+    assert [o["result"] for o in want] == [1, 0] and want[0]["vars"] != want[1]["vars"]
+    for k in range(8):
+        i = k % 2
+        r = eliminate(fs[i])
+        assert (r["result"], r["steps"], r["vars"]) == (want[i]["result"], want[i]["steps"], want[i]["vars"]), (k, i)
+
+
 def test_bench_random_unsat_set_matches_oracle():
     """The bench's configs[3] `rand-dp` set (16 random 3-SAT formulas n=16,
     m=96, seed 7002): verdicts, eliminated variables and every clause list."""

@@ -84,7 +84,7 @@ def test_pigeonhole_php43_four_passes(golden_dir):
 def test_repeated_calls_replay_the_captured_segment(golden_dir):
     """A call's first segment (state init, packing, seeding, the first batch of
     passes) is captured into a HIP graph the second time it repeats and
-    replayed after (csrc/resolution.hip ResGraph): the bench's php-res call
+    replayed after (csrc/resolution.hip ResGraphKey, host.h ReplayGraph): the bench's php-res call
     five times in a row, with other formulas in between (a new key: the
     segment is re-captured), adds the reference's sets every time."""
     with open(os.path.join(golden_dir, "resolution_php43.json")) as fh:
