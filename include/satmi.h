@@ -358,6 +358,62 @@ int satmi_cdcl_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
  * busy / (resident x span) is the launch's wave utilisation. */
 int satmi_cdcl_last_stats(double *span_s, double *busy_wave_s, int *resident_waves);
 
+/*
+ * Batched model check: evaluates assignment rows against their clause sets,
+ * one wavefront per instance, every row of an instance in turn (csrc/check.hip).
+ * The formulas are CSR arrays as above.  Instance b has `cap` row slots:
+ * row r is the first len[b * cap + r] ints of row_lits[(b * cap + r) * stride ..],
+ * signed literals -- the layout of satmi_dpll_batch_device's d_sol_len /
+ * d_sol_lits with sol_cap / sol_stride, and of satmi_cdcl_batch_host's
+ * h_assign_len / h_assign with cap = 1, so a device pipeline checks a solve's
+ * models on the same stream right after it, with no copy.
+ *   A literal l is TRUE if l is in the row, FALSE if -l is in the row and l is
+ *   not, else UNASSIGNED.  A clause is satisfied if some literal is true,
+ *   falsified if every literal is false (the empty clause always is), else
+ *   undetermined.  The rule is deterministic for malformed rows too: a repeated
+ *   literal counts once, and of a contradictory pair +v, -v both literals are
+ *   true.
+ *   max_vars       the truth table holds variables 1 .. max_vars, two bits each
+ *                  in the wavefront's LDS; at most SATMI_CHECK_MAX_VARS (a
+ *                  128 KiB table of the CU's 160 KiB), beyond which the call
+ *                  returns SATMI_ERR_TOO_LARGE before any launch.  A literal of
+ *                  a row with |l| > max_vars (or 0, INT32_MIN) is ignored and
+ *                  flagged; such a literal of the formula is unassigned.
+ *   max_clause_len longest clause of the batch, 0 = unknown: 1 .. 8 takes the
+ *                  lane-per-clause form, anything else the wave-per-clause form
+ *                  (same results)
+ *   rows           [B] rows to check per instance (clamped to 0 .. cap), NULL =
+ *                  cap; the rows from rows[b] on have their four words zeroed
+ *   len            [B x cap]; a length is clamped to 0 .. stride
+ *   out            [B x cap x SATMI_CHECK_NWORDS]: clauses falsified, clauses
+ *                  undetermined, index of the first falsified clause relative
+ *                  to the instance's first clause (-1: none), flags.  A row is
+ *                  a model iff words 0, 1 and 3 are all 0.
+ * The device form is asynchronous on `stream` (NULL = default stream) and owns
+ * no device memory.  The host form checks its arguments before any HIP call
+ * (num_instances == 0 returns SATMI_OK; a row count outside 0 .. cap or a
+ * length outside 0 .. stride is SATMI_ERR_ARG), computes max_vars over the
+ * formulas and the rows and max_clause_len itself, and is thread-safe: a call
+ * leases a workspace with its own stream, like satmi_resolution_batch_host.
+ * UNSAT answers get no certificate here.
+ */
+#define SATMI_CHECK_NWORDS 4          /* per row: falsified, undetermined, first_falsified (-1: none), flags */
+#define SATMI_CHECK_CONTRADICTORY 1   /* flags bit: some v with both +v and -v in the row */
+#define SATMI_CHECK_BAD_LITERAL 2     /* flags bit: a literal 0, INT32_MIN or |l| > max_vars (ignored) */
+#define SATMI_CHECK_MAX_VARS 524287   /* the largest max_vars: (524287 >> 4) + 1 = 32,768 table words */
+int satmi_check_models_device(int num_instances, const int32_t *d_inst_clause_begin,
+                              const int32_t *d_clause_lit_begin, const int32_t *d_lits, int max_vars,
+                              int max_clause_len, const int32_t *d_rows, const int32_t *d_len,
+                              const int32_t *d_row_lits, int cap, int stride, int32_t *d_out, void *stream);
+int satmi_check_models_host(int num_instances, const int32_t *h_inst_clause_begin,
+                            const int32_t *h_clause_lit_begin, const int32_t *h_lits, const int32_t *h_rows,
+                            const int32_t *h_len, const int32_t *h_row_lits, int cap, int stride, int32_t *h_out);
+
+/* Test knob of the model check (0 = default): at most `workgroups` workgroups
+ * are launched, of `waves_per_wg` (1, 2 or 4) wavefronts each, so a few dozen
+ * tiny instances exercise table reuse across instances and every region layout. */
+int satmi_check_debug_grid(int workgroups, int waves_per_wg);
+
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into
  * d_span: [0] = ~(first wave's start), [1] = last wave's end, so the launch

@@ -25,6 +25,12 @@ RES_BATCH_UNFIT = -2   # satmi_resolution_batch_host: the formula is left to sat
 DP_BATCH_UNFIT = -2    # satmi_dp_batch_host: the formula is left to satmi_dp_host
 RES_REGROWTHS = ("stage", "keys", "table", "chunks", "cand_reruns", "table_rebuilds", "clause_growths")
 KERNEL_AUTO, KERNEL_GENERAL, KERNEL_SCAN, KERNEL_INC, KERNEL_WIDE = 0, 1, 2, 3, 4
+ERR_ARG, ERR_HIP, ERR_TOO_LARGE, ERR_NOMEM = -1, -2, -3, -4
+# satmi_check_models_*: words per row, their names, the flags bits, the largest max_vars
+CHECK_NWORDS = 4
+CHECK_WORDS = ("falsified", "undetermined", "first_falsified", "flags")
+CHECK_CONTRADICTORY, CHECK_BAD_LITERAL = 1, 2
+CHECK_MAX_VARS = 524287
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
 EXPORTED = (
@@ -40,6 +46,7 @@ EXPORTED = (
     "satmi_dpll_split_busy", "satmi_dpll_scan_shape", "satmi_resolution_last_regrowths",
     "satmi_resolution_batch_host", "satmi_resolution_debug_batch",
     "satmi_dp_batch_host", "satmi_dp_debug_batch",
+    "satmi_check_models_device", "satmi_check_models_host", "satmi_check_debug_grid",
 )
 
 
@@ -165,6 +172,11 @@ def load():
         ctypes.c_int, i32p, i32p, i32p, ctypes.c_int64, ctypes.c_int64,
         i32p, i32p, i32p, i64p, ctypes.c_int, i32p, ctypes.c_int64, i64p, ctypes.c_int64, i64p]
     L.satmi_dp_debug_batch.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.satmi_check_models_device.argtypes = [ctypes.c_int, vp, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp,
+                                            ctypes.c_int, ctypes.c_int, vp, vp]
+    L.satmi_check_models_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, i32p, i32p, i32p,
+                                          ctypes.c_int, ctypes.c_int, i32p]
+    L.satmi_check_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = library/header mismatch
     _lib = L

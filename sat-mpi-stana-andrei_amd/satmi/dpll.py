@@ -42,6 +42,16 @@ class DpllResult:
     def counter_dict(self, b):
         return {n: int(self.counters[b, i]) for i, n in enumerate(_capi.COUNTER_NAMES[:7])}
 
+    def check(self, batch):
+        """The stored solutions evaluated against `batch` (the CnfBatch or formulas they
+        were found for) on the GPU: int32 [B, sol_cap, 4], _capi.CHECK_WORDS per row; the
+        rows past min(solutions, sol_cap) of an instance are zeros (satmi/check.py)."""
+        from .check import check_packed
+        if not isinstance(batch, CnfBatch):
+            batch = pack(batch)
+        rows = np.minimum(self.counters[:, 5], self.sol_len.shape[1]).astype(np.int32)
+        return check_packed(batch, rows, self.sol_len, self.sol_lits)
+
 
 def _ptr(a, t=ctypes.c_int32):
     return a.ctypes.data_as(ctypes.POINTER(t))

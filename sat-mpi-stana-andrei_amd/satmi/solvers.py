@@ -89,6 +89,14 @@ def dpll_solve(formula: Formula):
     return False, None
 
 
+def check_assignment(formula: Formula, assignment) -> bool:
+    """Whether `assignment` (a solver's dict {variable: bool}, or signed literals) is a
+    model of `formula`, evaluated on the GPU (satmi/check.py): every clause has a true
+    literal, and the assignment is neither contradictory nor malformed."""
+    from .check import check_models
+    return check_models([formula], [[assignment]])[0][0]["ok"]
+
+
 def resolution_solver(formula: Formula) -> bool:
     from .resolution import resolution_solve
     return resolution_solve(formula, time_limit=_time_limit)
