@@ -111,7 +111,14 @@ int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_clause_begi
                             int32_t *d_sol_lits, int32_t *d_root_len, int32_t *d_root_lits,
                             void *stream);
 
-/* Same, from host arrays (allocates, copies, runs, copies back; synchronous). */
+/* Same, from host arrays (allocates, copies, runs, copies back; synchronous).
+ * The arrays are checked first -- the count, the input pointers, both range
+ * arrays ascending from >= 0, no literal 0 / INT32_MIN, inst_nvars[b] >= 0, the
+ * init ranges and literals likewise -- and a malformed call is SATMI_ERR_ARG
+ * with the cause in satmi_last_error(), before any HIP call.  No literal of
+ * formula b may lie beyond inst_nvars[b] (the kernels size a formula's image by
+ * it); a larger inst_nvars[b] than the formula needs is allowed.  Output
+ * pointers that are NULL are outputs the caller does not want. */
 int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
                           const int32_t *h_clause_lit_begin, const int32_t *h_lits,
                           const int32_t *h_inst_nvars,
@@ -142,6 +149,10 @@ int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
  *   rec_pass_cap - 1 on are not recorded.  Nothing is written past an array's
  *   capacity.  *result, *passes and pass_new are not truncated by the record:
  *   pass_new[p] is exact for every p < pass_cap whatever was recorded.
+ * The arrays are checked first (nclauses >= 0, result and passes, with clauses
+ * both arrays, clause_off ascending from >= 0, no literal 0 / INT32_MIN): a
+ * malformed call is SATMI_ERR_ARG with the cause in satmi_last_error(), before
+ * any HIP call (a refused literal leaves *result = -1 and *passes = 0).
  */
 int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, const int32_t *h_lits,
                           int64_t max_passes, int64_t clause_limit, double time_limit_s,
@@ -237,6 +248,9 @@ int satmi_resolution_debug_batch(int grid, int key_cap);
  * Thread-safe: a call takes a device workspace (buffers kept between calls,
  * its own HIP stream) from a process-wide pool and returns it, so solves from
  * several threads overlap and memory is bounded by the peak concurrency.
+ * The arrays are checked first, as satmi_resolution_host checks them: a
+ * malformed call is SATMI_ERR_ARG before any HIP call (a refused literal leaves
+ * *result = -1 and *steps = 0).
  */
 int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const int32_t *h_lits, int64_t step_limit,
                   int64_t clause_limit, double time_limit_s, int32_t *h_result, int32_t *h_trace_vars,
@@ -340,6 +354,10 @@ int satmi_resolution_trim(void);
  *                 decisions, learned clauses, formula length, watch-list keys,
  *                 decision level, set-table slots used
  *   h_var_inc[b]  the solver's var_inc at the end
+ * The arrays are checked first (the count, assign_stride, every pointer of a
+ * non-empty batch, both range arrays ascending from >= 0, no literal 0 /
+ * INT32_MIN): a malformed call is SATMI_ERR_ARG with the cause in
+ * satmi_last_error(), before any HIP call.
  */
 #define SATMI_CDCL_UNSAT 0
 #define SATMI_CDCL_SAT 1

@@ -1,13 +1,29 @@
-// batch_host.h -- the launch-side pieces the two batched entry points
-// (resolution_batch.hip, dp_batch.hip) share: the workspace a call leases, the
-// persistent grid's size, the dynamic-LDS attribute (its blocks are carved with
-// host.h's Carve).
-// The launch sequences differ (Davis-Putnam launches twice when it records).
+// batch_host.h -- the device-side pieces the batched entry points share: the
+// staging of one carved block (dpll.hip, cdcl.hip), and for the entry points
+// with a persistent grid (resolution_batch.hip, dp_batch.hip, check.hip) the
+// workspace a call leases, the grid's size and the dynamic-LDS attribute.
+// Blocks are carved with host.h's Carve; the launch sequences differ.
 #pragma once
 #include "batch_keys.h"
 #include "host.h"
 
 namespace satmi {
+
+// One device block carved with Carve, and the stream its copies go on.
+struct Staged {
+    unsigned char *base;
+    hipStream_t stream;
+    template <class T>
+    T *at(size_t off) const { return (T *)(base + off); }
+    int up(size_t off, const void *src, size_t bytes) const {
+        if (bytes) SATMI_HIP(hipMemcpyAsync(base + off, src, bytes, hipMemcpyHostToDevice, stream));
+        return SATMI_OK;
+    }
+    int down(void *dst, size_t off, size_t bytes) const {   // a null `dst` is an output the caller does not want
+        if (dst && bytes) SATMI_HIP(hipMemcpyAsync(dst, base + off, bytes, hipMemcpyDeviceToHost, stream));
+        return SATMI_OK;
+    }
+};
 
 // A call's device state, kept between calls in the workspace pool (host.h; one
 // pool per entry point: each derives its own empty type).  Nothing in it is

@@ -38,8 +38,8 @@
 #include <climits>
 #include <vector>
 
+#include "batch_host.h"
 #include "common.h"
-#include "host.h"
 
 namespace satmi {
 namespace {
@@ -901,26 +901,25 @@ bool make_cdcl_layout(int max_vars, int64_t max_clauses, int64_t max_lits, int m
     // set tables: each clause sits in <= 2 sets; a table is < 8x its entries
     // over its lifetime (doubling tables, dummies until the next resize)
     const int64_t P = 16 * 2 * C + (int64_t)WS_MINSIZE * K;
-    auto a = [](uint64_t x) { return (x + 255u) & ~(uint64_t)255u; };
-    uint64_t o = 0;
-    L->coff = o;    o = a(o + 4 * (uint64_t)(C + 1));
-    L->lits = o;    o = a(o + 4 * (uint64_t)Lc);
-    L->val = o;     o = a(o + (uint64_t)N);
-    L->ord = o;     o = a(o + 8 * (uint64_t)N);
-    L->lev = o;     o = a(o + 4 * (uint64_t)N);
-    L->ante = o;    o = a(o + 4 * (uint64_t)N);
-    L->act = o;     o = a(o + 8 * (uint64_t)N);
-    L->appears = o; o = a(o + 8 * (uint64_t)(N / 64 + 1));
-    L->klit = o;    o = a(o + 4 * (uint64_t)K);
-    L->kidx = o;    o = a(o + 4 * (uint64_t)K);
-    L->woff = o;    o = a(o + 4 * (uint64_t)K);
-    L->wmask = o;   o = a(o + 4 * (uint64_t)K);
-    L->wfill = o;   o = a(o + 4 * (uint64_t)K);
-    L->wused = o;   o = a(o + 4 * (uint64_t)K);
-    L->pool = o;    o = a(o + 4 * (uint64_t)P);
+    Carve cv;
+    L->coff = cv.take(4 * (size_t)(C + 1));
+    L->lits = cv.take(4 * (size_t)Lc);
+    L->val = cv.take((size_t)N);
+    L->ord = cv.take(8 * (size_t)N);
+    L->lev = cv.take(4 * (size_t)N);
+    L->ante = cv.take(4 * (size_t)N);
+    L->act = cv.take(8 * (size_t)N);
+    L->appears = cv.take(8 * (size_t)(N / 64 + 1));
+    L->klit = cv.take(4 * (size_t)K);
+    L->kidx = cv.take(4 * (size_t)K);
+    L->woff = cv.take(4 * (size_t)K);
+    L->wmask = cv.take(4 * (size_t)K);
+    L->wfill = cv.take(4 * (size_t)K);
+    L->wused = cv.take(4 * (size_t)K);
+    L->pool = cv.take(4 * (size_t)P);
     L->lcap = (int32_t)std::min<int64_t>(2 * N + 2 + std::max(max_len, 1), INT32_MAX / 8);
-    L->scratch = o; o = a(o + 4 * 2 * (uint64_t)L->lcap);   // two learned-literal lists
-    L->bytes = o;
+    L->scratch = cv.take(4 * 2 * (size_t)L->lcap);   // two learned-literal lists
+    L->bytes = cv.at;
     const uint64_t small = L->pool - L->val, lds = small + 4 * 2 * (uint64_t)L->lcap;
     L->lds_bytes = lds <= CDCL_LDS_MAX ? (uint32_t)lds : 0u;
     L->lds_scratch = (uint32_t)small;
@@ -960,47 +959,22 @@ extern "C" int satmi_cdcl_batch_host(int num_instances, const int32_t *h_inst_cl
                                      int64_t learn_cap, double time_limit_s, int32_t *h_status,
                                      int32_t *h_assign_len, int32_t *h_assign, int assign_stride,
                                      int64_t *h_stats, double *h_var_inc) {
-    if (num_instances < 0 || !h_inst_clause_begin || !h_clause_lit_begin || !h_status || !h_assign_len ||
-        !h_assign || !h_stats || !h_var_inc || assign_stride < 0) {
-        set_error("satmi_cdcl_batch_host: bad arguments");
-        return SATMI_ERR_ARG;
-    }
+    const char *who = "satmi_cdcl_batch_host";
+    // ---- check: all of it before any HIP call
+    CsrShape sh;
+    std::vector<int32_t> nv((size_t)std::max(num_instances, 0));
+    if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits,
+                                          assign_stride < 0 ? "negative assign_stride" : nullptr,
+                                          h_status && h_assign_len && h_assign && h_stats && h_var_inc, &sh, nv.data()))
+        return fail_arg(who, bad);
     if (num_instances == 0) return SATMI_OK;
-    const int C = h_inst_clause_begin[num_instances];
-    const int Ltot = h_clause_lit_begin[C];
-    std::vector<int32_t> nv(num_instances, 0);
-    int max_vars = 0, max_len = 0;
-    int64_t max_clauses = 0, max_lits = 0;
-    // (flat loops without early exits: the compiler vectorises them; a batch of
-    // 32,768 menu formulas is ~5 M literals, scanned on the host every call)
-    for (int c = 0; c < C; ++c) max_len = std::max(max_len, h_clause_lit_begin[c + 1] - h_clause_lit_begin[c]);
-    int bad = 0;
-    for (int b = 0; b < num_instances; ++b) {
-        const int cb = h_inst_clause_begin[b], ce = h_inst_clause_begin[b + 1];
-        const int lb = h_clause_lit_begin[cb], le = h_clause_lit_begin[ce];
-        max_clauses = std::max<int64_t>(max_clauses, ce - cb);
-        max_lits = std::max<int64_t>(max_lits, le - lb);
-        uint32_t m = 0;
-        for (int j = lb; j < le; ++j) {
-            const int x = h_lits[j];
-            bad |= (x == 0) | (x == INT32_MIN);
-            m = std::max(m, x < 0 ? 0u - (uint32_t)x : (uint32_t)x);   // (INT32_MIN rejected below)
-        }
-        nv[b] = (int)std::min<uint32_t>(m, INT32_MAX);
-        max_vars = std::max(max_vars, nv[b]);
-    }
-    if (bad) {
-        set_error("satmi_cdcl_batch_host: literal 0 / INT32_MIN");
-        return SATMI_ERR_ARG;
-    }
-    if (assign_stride < max_vars) {
-        set_error("satmi_cdcl_batch_host: assign_stride < number of variables");
-        return SATMI_ERR_ARG;
-    }
+    const int C = sh.C, Ltot = (int)sh.Ltot;
+    const int max_vars = *std::max_element(nv.begin(), nv.end());   // (of the formulas: sh.max_var is the arrays')
+    if (assign_stride < max_vars) return fail_arg(who, "assign_stride < number of variables");
     // learned clauses: one per conflict, at most one per iteration
     if (learn_cap <= 0) learn_cap = max_iter > 0 ? max_iter : (1 << 16);
     CdclLayout lay;
-    if (!make_cdcl_layout(max_vars, max_clauses, max_lits, max_len, learn_cap, &lay)) {
+    if (!make_cdcl_layout(max_vars, sh.max_clauses, sh.max_lits, sh.max_len, learn_cap, &lay)) {
         set_error("satmi_cdcl_batch_host: instance too large");
         return SATMI_ERR_TOO_LARGE;
     }
@@ -1016,78 +990,69 @@ extern "C" int satmi_cdcl_batch_host(int num_instances, const int32_t *h_inst_cl
         return SATMI_ERR_NOMEM;
     }
     const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)facts.cus * 32, by_mem});
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_icb = 0, o_clb = o_icb + up(4 * (size_t)(num_instances + 1));
-    const size_t o_lits = o_clb + up(4 * (size_t)(C + 1));
-    const size_t o_nv = o_lits + up(4 * (size_t)std::max(Ltot, 1));
-    const size_t o_st = o_nv + up(4 * (size_t)num_instances);
-    const size_t o_al = o_st + up(4 * (size_t)num_instances);
-    const size_t o_as = o_al + up(4 * (size_t)num_instances);
-    const size_t o_stats = o_as + up(4 * (size_t)num_instances * std::max(assign_stride, 1));
-    const size_t o_vi = o_stats + up(8 * (size_t)num_instances * SATMI_CDCL_NSTATS);
-    const size_t o_wc = o_vi + up(8 * (size_t)num_instances);
-    const size_t o_arena = o_wc + 256;
-    const size_t total = o_arena + (size_t)grid * (size_t)lay.bytes;
+    const size_t B = (size_t)num_instances;
+    Carve cv;
+    const size_t o_icb = cv.take(4 * (B + 1));
+    const size_t o_clb = cv.take(4 * (size_t)(C + 1));
+    const size_t o_lits = cv.take(4 * (size_t)std::max(Ltot, 1));
+    const size_t o_nv = cv.take(4 * B);
+    const size_t o_st = cv.take(4 * B);
+    const size_t o_al = cv.take(4 * B);
+    const size_t o_as = cv.take(4 * B * (size_t)std::max(assign_stride, 1));
+    const size_t o_stats = cv.take(8 * B * SATMI_CDCL_NSTATS);
+    const size_t o_vi = cv.take(8 * B);
+    const size_t o_wc = cv.take(256);   // counter, span (common.h), busy ticks
+    const size_t o_arena = cv.at;
     Lease<CdclSlot> lease{Pool<CdclSlot>::get().acquire(dev)};
     if (!lease.w) {
         set_error("satmi_cdcl_batch_host: hipStreamCreate failed");
         return SATMI_ERR_HIP;
     }
     lease.ok = true;   // whatever the call's outcome (see CdclSlot)
-    SATMI_TRY(lease.w->mem.reserve(total));
-    unsigned char *d = lease.w->mem.as<unsigned char>();
-    hipStream_t s = lease.w->stream;
-    int rc = SATMI_OK;
-    do {
-        auto h2d = [&](size_t off, const void *src, size_t bytes) {
-            return bytes ? hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
-        };
-        if (h2d(o_icb, h_inst_clause_begin, 4 * (size_t)(num_instances + 1)) != hipSuccess ||
-            h2d(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)) != hipSuccess ||
-            h2d(o_lits, h_lits, 4 * (size_t)Ltot) != hipSuccess ||
-            h2d(o_nv, nv.data(), 4 * (size_t)num_instances) != hipSuccess ||
-            hipMemsetAsync(d + o_wc, 0, 32, s) != hipSuccess) {   // counter, span (common.h), busy ticks
-            rc = hip_fail(hipGetLastError(), "satmi_cdcl_batch_host: staging");
-            break;
-        }
-        CdclArgs A;
-        A.inst_clause_begin = (const int32_t *)(d + o_icb);
-        A.clause_lit_begin = (const int32_t *)(d + o_clb);
-        A.lits = (const int32_t *)(d + o_lits);
-        A.inst_nvars = (const int32_t *)(d + o_nv);
-        A.num_instances = num_instances;
-        A.max_iter = max_iter;
-        A.time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * ticks_per_s) : 0;
-        A.status = (int32_t *)(d + o_st);
-        A.assign_len = (int32_t *)(d + o_al);
-        A.assign = (int32_t *)(d + o_as);
-        A.assign_stride = assign_stride;
-        A.stats = (int64_t *)(d + o_stats);
-        A.var_inc = (double *)(d + o_vi);
-        A.arena = d + o_arena;
-        A.lay = lay;
-        A.work_counter = (uint32_t *)(d + o_wc);
-        if (lay.lds_bytes)
-            hipLaunchKernelGGL(cdcl_kernel<true>, dim3(grid), dim3(64), lay.lds_bytes, s, A);
-        else
-            hipLaunchKernelGGL(cdcl_kernel<false>, dim3(grid), dim3(64), 0, s, A);
-        hipError_t e = hipGetLastError();
-        auto d2h = [&](void *dst, size_t off, size_t bytes) {
-            if (e == hipSuccess && bytes) e = hipMemcpyAsync(dst, d + off, bytes, hipMemcpyDeviceToHost, s);
-        };
-        d2h(h_status, o_st, 4 * (size_t)num_instances);
-        d2h(h_assign_len, o_al, 4 * (size_t)num_instances);
-        d2h(h_assign, o_as, 4 * (size_t)num_instances * assign_stride);
-        d2h(h_stats, o_stats, 8 * (size_t)num_instances * SATMI_CDCL_NSTATS);
-        d2h(h_var_inc, o_vi, 8 * (size_t)num_instances);
-        uint64_t wc[4] = {0, 0, 0, 0};
-        d2h(wc, o_wc, sizeof(wc));
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = hip_fail(e, "satmi_cdcl_batch_host: launch / copy back");
-        g_cdcl_stats.span_s = (double)(wc[2] - ~wc[1]) / ticks_per_s;
-        g_cdcl_stats.busy_wave_s = (double)wc[3] / ticks_per_s;
-        g_cdcl_stats.resident_waves = grid;
-    } while (0);
+    SATMI_TRY(lease.w->mem.reserve(o_arena + (size_t)grid * (size_t)lay.bytes));
+    const Staged d{lease.w->mem.as<unsigned char>(), lease.w->stream};
+    SATMI_TRY(d.up(o_icb, h_inst_clause_begin, 4 * (B + 1)));
+    SATMI_TRY(d.up(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)));
+    SATMI_TRY(d.up(o_lits, h_lits, 4 * (size_t)Ltot));
+    SATMI_TRY(d.up(o_nv, nv.data(), 4 * B));
+    SATMI_HIP(hipMemsetAsync(d.base + o_wc, 0, 32, d.stream));
+    CdclArgs A;
+    A.inst_clause_begin = d.at<const int32_t>(o_icb);
+    A.clause_lit_begin = d.at<const int32_t>(o_clb);
+    A.lits = d.at<const int32_t>(o_lits);
+    A.inst_nvars = d.at<const int32_t>(o_nv);
+    A.num_instances = num_instances;
+    A.max_iter = max_iter;
+    A.time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * ticks_per_s) : 0;
+    A.status = d.at<int32_t>(o_st);
+    A.assign_len = d.at<int32_t>(o_al);
+    A.assign = d.at<int32_t>(o_as);
+    A.assign_stride = assign_stride;
+    A.stats = d.at<int64_t>(o_stats);
+    A.var_inc = d.at<double>(o_vi);
+    A.arena = d.base + o_arena;
+    A.lay = lay;
+    A.work_counter = d.at<uint32_t>(o_wc);
+    if (lay.lds_bytes)
+        hipLaunchKernelGGL(cdcl_kernel<true>, dim3(grid), dim3(64), lay.lds_bytes, d.stream, A);
+    else
+        hipLaunchKernelGGL(cdcl_kernel<false>, dim3(grid), dim3(64), 0, d.stream, A);
+    uint64_t wc[4] = {0, 0, 0, 0};
+    const auto copy_back = [&]() -> int {
+        SATMI_HIP(hipGetLastError());
+        SATMI_TRY(d.down(h_status, o_st, 4 * B));
+        SATMI_TRY(d.down(h_assign_len, o_al, 4 * B));
+        SATMI_TRY(d.down(h_assign, o_as, 4 * B * (size_t)assign_stride));
+        SATMI_TRY(d.down(h_stats, o_stats, 8 * B * SATMI_CDCL_NSTATS));
+        SATMI_TRY(d.down(h_var_inc, o_vi, 8 * B));
+        SATMI_TRY(d.down(wc, o_wc, sizeof(wc)));
+        SATMI_HIP(hipStreamSynchronize(d.stream));
+        return SATMI_OK;
+    };
+    const int rc = copy_back();   // (the stats of a launch that failed are those of the zeroed words)
+    g_cdcl_stats.span_s = (double)(wc[2] - ~wc[1]) / ticks_per_s;
+    g_cdcl_stats.busy_wave_s = (double)wc[3] / ticks_per_s;
+    g_cdcl_stats.resident_waves = grid;
     return rc;
 }
 

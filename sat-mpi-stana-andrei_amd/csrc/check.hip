@@ -192,11 +192,6 @@ std::atomic<int> g_dbg_grid{0}, g_dbg_wpg{0};   // satmi_check_debug_grid
 
 struct CheckWork : BatchWork {};   // a pool of its own (keys_out, rec_off stay empty)
 
-int fail_arg(const char *who, const char *what) {
-    set_error(std::string(who) + ": " + what);
-    return SATMI_ERR_ARG;
-}
-
 int too_large(const char *who, int64_t max_vars) {
     set_error(std::string(who) + ": variable " + std::to_string(max_vars) + " is beyond the table's " +
               std::to_string(SATMI_CHECK_MAX_VARS));
@@ -287,18 +282,16 @@ extern "C" int satmi_check_models_host(int num_instances, const int32_t *h_inst_
                                        int cap, int stride, int32_t *h_out) {
     const char *who = "satmi_check_models_host";
     // ---- check: all of it before any HIP call
+    CsrShape sh;
     if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits,
                                           cap < 1 ? "cap < 1" : stride < 1 ? "stride < 1" : nullptr,
-                                          h_len && h_row_lits && h_out))
+                                          h_len && h_row_lits && h_out, &sh))
         return fail_arg(who, bad);
     if (num_instances == 0) return SATMI_OK;
-    const int B = num_instances, C = h_inst_clause_begin[B];
-    const int64_t L0 = h_clause_lit_begin[0], Ltot = h_clause_lit_begin[C];
+    const int B = num_instances, C = sh.C, max_clause_len = sh.max_len;
+    const int64_t Ltot = sh.Ltot;
     const size_t nrow = (size_t)B * (size_t)cap;
-    int64_t max_vars = 0;
-    int max_clause_len = 0;
-    for (int64_t j = L0; j < Ltot; ++j) max_vars = std::max<int64_t>(max_vars, std::abs((int64_t)h_lits[j]));
-    for (int c = 0; c < C; ++c) max_clause_len = std::max(max_clause_len, h_clause_lit_begin[c + 1] - h_clause_lit_begin[c]);
+    int64_t max_vars = sh.max_var;
     for (int b = 0; b < B; ++b) {
         const int nr = h_rows ? h_rows[b] : cap;
         if (nr < 0 || nr > cap) return fail_arg(who, "row count outside 0 .. cap");

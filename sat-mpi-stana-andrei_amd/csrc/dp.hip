@@ -58,6 +58,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "batch_keys.h"
 #include "common.h"
 #include "host.h"
 #include "prims.h"
@@ -1994,19 +1995,19 @@ extern "C" int satmi_dp_host(int nclauses, const int32_t *h_clause_off, const in
                              int trace_cap, int32_t *h_steps, int32_t *h_rec_lits, int64_t rec_lit_cap,
                              int64_t *h_rec_clause_off, int64_t rec_clause_cap, int64_t *h_rec_step_off,
                              int rec_step_cap) {
-    if (nclauses < 0 || (nclauses > 0 && (!h_clause_off || !h_lits)) || !h_result || !h_steps) {
-        set_error("satmi_dp_host: bad arguments");
-        return SATMI_ERR_ARG;
-    }
+    // the check, before any HIP call (a bad literal is refused after the outputs were reset)
+    CsrShape sh;
+    const char *bad = formula_csr_check(nclauses, h_clause_off, h_lits, nullptr, h_result && h_steps, &sh);
+    if (bad && bad != CSR_BAD_LITERAL) return fail_arg("satmi_dp_host", bad);
     *h_result = -1;
     *h_steps = 0;
     if (h_rec_step_off && rec_step_cap > 0) h_rec_step_off[0] = 0;
     if (h_rec_clause_off && rec_clause_cap > 0) h_rec_clause_off[0] = 0;
-    const int64_t Ltot = nclauses > 0 ? h_clause_off[nclauses] : 0;
-    int maxvar = 0, maxlen = 0;
-    for (int c = 0; c < nclauses; ++c) maxlen = std::max(maxlen, h_clause_off[c + 1] - h_clause_off[c]);
+    if (bad) return fail_arg("satmi_dp_host", bad);
+    const int64_t Ltot = sh.Ltot;
+    const int maxvar = sh.max_var, maxlen = sh.max_len;
     std::vector<int32_t> var2dense, dense2var;
-    SATMI_TRY(dense_var_index("satmi_dp_host", h_lits, Ltot, &maxvar, &var2dense, &dense2var));
+    dense_var_index(h_lits, sh.L0, Ltot, maxvar, &var2dense, &dense2var);
     const int V = (int)dense2var.size();
     g_dp_stats = DpStats{};
     if (V == 0) {   // no variables: `while variables` never runs -- True (REF.py:130)

@@ -47,8 +47,8 @@
 #include <string>
 #include <vector>
 
+#include "batch_host.h"
 #include "common.h"
-#include "host.h"
 #include "dpll_scan.h"
 
 namespace satmi {
@@ -1309,37 +1309,40 @@ extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_cl
                                      int64_t node_limit, double time_limit_s, int sol_cap, int sol_stride,
                                      int32_t *h_status, int64_t *h_counters, int32_t *h_sol_len,
                                      int32_t *h_sol_lits, int32_t *h_root_len, int32_t *h_root_lits) {
-    if (num_instances < 0 || !h_inst_clause_begin || !h_clause_lit_begin || !h_inst_nvars) {
-        set_error("satmi_dpll_batch_host: bad arguments");
-        return SATMI_ERR_ARG;
-    }
+    const char *who = "satmi_dpll_batch_host";
+    // ---- check: all of it before any HIP call
+    CsrShape sh;
+    std::vector<int32_t> nv((size_t)std::max(num_instances, 0));
+    if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits, nullptr,
+                                          h_inst_nvars != nullptr, &sh, nv.data()))
+        return fail_arg(who, bad);
     if (num_instances == 0) return SATMI_OK;
-    const int C = h_inst_clause_begin[num_instances];
-    const int Ltot = h_clause_lit_begin[C];
-    int max_vars = 0, max_clauses = 0, max_lits = 0, max_len = 0, min_len = INT_MAX;
-    for (int c = 0; c < C; ++c) {
-        const int len = h_clause_lit_begin[c + 1] - h_clause_lit_begin[c];
-        max_len = std::max(max_len, len);
-        min_len = std::min(min_len, len);
-    }
+    const int C = sh.C, Ltot = (int)sh.Ltot, max_len = sh.max_len, min_len = sh.min_len;
     // the scan kernel needs every clause non-empty: report 0 (unknown) otherwise.
     // Past 5 literals no clause kernel is eligible, and the true length is what
     // keeps a long clause beside an empty one out of the LDS form.
     const int max_clause_len = (C > 0 && (min_len >= 1 || max_len > 5)) ? max_len : 0;
+    // the kernels size a formula's image by inst_nvars: no literal lies beyond it
+    int max_vars = 0;
     for (int b = 0; b < num_instances; ++b) {
-        const int cb = h_inst_clause_begin[b], ce = h_inst_clause_begin[b + 1];
-        max_clauses = std::max(max_clauses, ce - cb);
-        max_lits = std::max(max_lits, h_clause_lit_begin[ce] - h_clause_lit_begin[cb]);
+        if (h_inst_nvars[b] < 0) return fail_arg(who, "negative inst_nvars");
+        if (nv[(size_t)b] > h_inst_nvars[b]) return fail_arg(who, "literal beyond inst_nvars");
         max_vars = std::max(max_vars, h_inst_nvars[b]);
     }
-    const int Itot = h_init_begin ? h_init_begin[num_instances] : 0;
-    if (h_init_begin)
-        for (int i = 0; i < Itot; ++i) max_vars = std::max(max_vars, std::abs(h_init_lits[i]));
-    if (sol_stride < max_vars) {
-        set_error("satmi_dpll_batch_host: sol_stride < number of variables");
-        return SATMI_ERR_ARG;
+    int Itot = 0;
+    if (h_init_begin) {
+        if (h_init_begin[0] < 0) return fail_arg(who, "init ranges are not ascending");
+        for (int b = 0; b < num_instances; ++b)
+            if (h_init_begin[b + 1] < h_init_begin[b]) return fail_arg(who, "init ranges are not ascending");
+        Itot = h_init_begin[num_instances];
+        if (Itot > 0 && !h_init_lits) return fail_arg(who, "null pointer");
+        for (int i = 0; i < Itot; ++i) {
+            if (h_init_lits[i] == 0 || h_init_lits[i] == INT32_MIN) return fail_arg(who, "init literal 0 / INT32_MIN");
+            max_vars = std::max(max_vars, std::abs(h_init_lits[i]));
+        }
     }
-    // one allocation for everything, freed on every way out
+    if (sol_stride < max_vars) return fail_arg(who, "sol_stride < number of variables");
+    // ---- stage, launch, copy back: one allocation for everything, freed on every way out
     const size_t B = (size_t)num_instances;
     const size_t cap1 = (size_t)std::max(sol_cap, 1), stride1 = (size_t)std::max(sol_stride, 1);
     Carve cv;
@@ -1357,39 +1360,30 @@ extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_cl
     const size_t o_rlits = cv.take(4 * B * stride1);
     DevBuf buf;
     SATMI_TRY(buf.reserve(cv.at));
-    unsigned char *d = buf.as<unsigned char>();
-    hipStream_t s = nullptr;
-    auto h2d = [&](size_t off, const void *src, size_t bytes) -> int {
-        if (bytes) SATMI_HIP(hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, s));
-        return SATMI_OK;
-    };
-    auto d2h = [&](void *dst, size_t off, size_t bytes) -> int {
-        if (dst && bytes) SATMI_HIP(hipMemcpyAsync(dst, d + off, bytes, hipMemcpyDeviceToHost, s));
-        return SATMI_OK;
-    };
-    SATMI_TRY(h2d(o_icb, h_inst_clause_begin, 4 * (B + 1)));
-    SATMI_TRY(h2d(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)));
-    SATMI_TRY(h2d(o_lits, h_lits, 4 * (size_t)Ltot));
-    SATMI_TRY(h2d(o_nv, h_inst_nvars, 4 * B));
+    const Staged d{buf.as<unsigned char>(), nullptr};
+    SATMI_TRY(d.up(o_icb, h_inst_clause_begin, 4 * (B + 1)));
+    SATMI_TRY(d.up(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)));
+    SATMI_TRY(d.up(o_lits, h_lits, 4 * (size_t)Ltot));
+    SATMI_TRY(d.up(o_nv, h_inst_nvars, 4 * B));
     if (h_init_begin) {
-        SATMI_TRY(h2d(o_ib, h_init_begin, 4 * (B + 1)));
-        SATMI_TRY(h2d(o_il, h_init_lits, 4 * (size_t)Itot));
+        SATMI_TRY(d.up(o_ib, h_init_begin, 4 * (B + 1)));
+        SATMI_TRY(d.up(o_il, h_init_lits, 4 * (size_t)Itot));
     }
     SATMI_TRY(satmi_dpll_batch_device(
-        num_instances, (const int32_t *)(d + o_icb), (const int32_t *)(d + o_clb), (const int32_t *)(d + o_lits),
-        (const int32_t *)(d + o_nv), max_vars, max_clauses, max_lits, max_clause_len,
-        h_init_begin ? (const int32_t *)(d + o_ib) : nullptr, h_init_begin ? (const int32_t *)(d + o_il) : nullptr,
-        mode, max_solutions, node_limit, time_limit_s, sol_cap, sol_stride, (int32_t *)(d + o_st),
-        (int64_t *)(d + o_ctr), (int32_t *)(d + o_sl), (int32_t *)(d + o_sol), (int32_t *)(d + o_rl),
-        (int32_t *)(d + o_rlits), s));
-    SATMI_TRY(d2h(h_status, o_st, 4 * B));
-    SATMI_TRY(d2h(h_counters, o_ctr, 8 * B * SATMI_NCOUNTERS));
+        num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
+        d.at<const int32_t>(o_nv), max_vars, sh.max_clauses, sh.max_lits, max_clause_len,
+        h_init_begin ? d.at<const int32_t>(o_ib) : nullptr, h_init_begin ? d.at<const int32_t>(o_il) : nullptr,
+        mode, max_solutions, node_limit, time_limit_s, sol_cap, sol_stride, d.at<int32_t>(o_st),
+        d.at<int64_t>(o_ctr), d.at<int32_t>(o_sl), d.at<int32_t>(o_sol), d.at<int32_t>(o_rl),
+        d.at<int32_t>(o_rlits), d.stream));
+    SATMI_TRY(d.down(h_status, o_st, 4 * B));
+    SATMI_TRY(d.down(h_counters, o_ctr, 8 * B * SATMI_NCOUNTERS));
     if (sol_cap > 0) {
-        SATMI_TRY(d2h(h_sol_len, o_sl, 4 * B * (size_t)sol_cap));
-        SATMI_TRY(d2h(h_sol_lits, o_sol, 4 * B * (size_t)sol_cap * (size_t)sol_stride));
+        SATMI_TRY(d.down(h_sol_len, o_sl, 4 * B * (size_t)sol_cap));
+        SATMI_TRY(d.down(h_sol_lits, o_sol, 4 * B * (size_t)sol_cap * (size_t)sol_stride));
     }
-    SATMI_TRY(d2h(h_root_len, o_rl, 4 * B));
-    SATMI_TRY(d2h(h_root_lits, o_rlits, 4 * B * (size_t)sol_stride));
-    const hipError_t e = hipStreamSynchronize(s);
+    SATMI_TRY(d.down(h_root_len, o_rl, 4 * B));
+    SATMI_TRY(d.down(h_root_lits, o_rlits, 4 * B * (size_t)sol_stride));
+    const hipError_t e = hipStreamSynchronize(d.stream);
     return e == hipSuccess ? SATMI_OK : hip_fail(e, "hipStreamSynchronize");
 }

@@ -4,9 +4,9 @@
 // and carving of layouts, the cached device facts, the grow-only device and
 // pinned buffers, the workspace pool with its lease and the stream a workspace
 // owns, event-pair timing, capture-then-replay of a repeated launch segment,
-// the dense variable index, and the DPLL launches' per-stream state (the two
-// batched entry points share batch_keys.h and batch_host.h besides).  Host
-// code only; device helpers are in common.h.
+// the dense variable index, and the DPLL launches' per-stream state (the check
+// of host arrays is batch_keys.h, what the batched entry points share besides
+// is batch_host.h).  Host code only; device helpers are in common.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -29,6 +29,12 @@ namespace satmi {
         int _rc = (x);                   \
         if (_rc != SATMI_OK) return _rc; \
     } while (0)
+
+// A refused argument, under the entry point's name `who`.
+inline int fail_arg(const char *who, const char *what) {
+    set_error(std::string(who) + ": " + what);
+    return SATMI_ERR_ARG;
+}
 
 constexpr uint32_t LDS_PER_CU = 160u * 1024u;   // bytes of LDS a CU's workgroups share
 
@@ -345,29 +351,20 @@ struct ReplayGraph {
 };
 
 // ---------------------------------------------------------------- dense variable index
-// Checks the literals of a formula (0 and INT32_MIN are errors, reported under
-// the caller's name `who`) and numbers the variables that occur, in ascending
-// order of their ids: var2dense[v] = index or -1, dense2var[index] = v.
-inline int dense_var_index(const char *who, const int32_t *lits, int64_t nlits, int *maxvar,
-                           std::vector<int32_t> *var2dense, std::vector<int32_t> *dense2var) {
-    int mv = 0;
-    for (int64_t i = 0; i < nlits; ++i) {
-        if (lits[i] == 0 || lits[i] == INT32_MIN) {
-            set_error(std::string(who) + ": literal 0 / INT32_MIN");
-            return SATMI_ERR_ARG;
-        }
-        mv = std::max(mv, std::abs(lits[i]));
-    }
-    var2dense->assign((size_t)mv + 1, -1);
+// Numbers the variables that occur in the checked literals lits[lo .. hi) of a
+// formula (batch_keys.h: none is 0 or INT32_MIN, `maxvar` is their largest
+// variable), in ascending order of their ids: var2dense[v] = index or -1,
+// dense2var[index] = v.
+inline void dense_var_index(const int32_t *lits, int64_t lo, int64_t hi, int maxvar,
+                            std::vector<int32_t> *var2dense, std::vector<int32_t> *dense2var) {
+    var2dense->assign((size_t)maxvar + 1, -1);
     dense2var->clear();
-    for (int64_t i = 0; i < nlits; ++i) (*var2dense)[std::abs(lits[i])] = 1;
-    for (int v = 1; v <= mv; ++v)
+    for (int64_t i = lo; i < hi; ++i) (*var2dense)[std::abs(lits[i])] = 1;
+    for (int v = 1; v <= maxvar; ++v)
         if ((*var2dense)[v] >= 0) {
             (*var2dense)[v] = (int32_t)dense2var->size();
             dense2var->push_back(v);
         }
-    *maxvar = mv;
-    return SATMI_OK;
 }
 
 // ---------------------------------------------------------------- DPLL stream state

@@ -38,6 +38,7 @@
 #include <string>
 #include <vector>
 
+#include "batch_keys.h"
 #include "common.h"
 #include "host.h"
 #include "prims.h"
@@ -1088,10 +1089,10 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
                                      int32_t *h_result, int32_t *h_passes, int64_t *h_pass_new, int pass_cap,
                                      int32_t *h_rec_lits, int64_t rec_lit_cap, int64_t *h_rec_clause_off,
                                      int64_t rec_clause_cap, int64_t *h_rec_pass_off, int rec_pass_cap) {
-    if (nclauses < 0 || (nclauses > 0 && (!h_clause_off || !h_lits)) || !h_result || !h_passes) {
-        set_error("satmi_resolution_host: bad arguments");
-        return SATMI_ERR_ARG;
-    }
+    // the check, before any HIP call (a bad literal is refused after the outputs were reset)
+    CsrShape sh;
+    const char *bad = formula_csr_check(nclauses, h_clause_off, h_lits, nullptr, h_result && h_passes, &sh);
+    if (bad && bad != CSR_BAD_LITERAL) return fail_arg("satmi_resolution_host", bad);
     const auto t_start = std::chrono::steady_clock::now();
     const auto expired = [&]() {
         return time_limit_s > 0 &&
@@ -1101,11 +1102,12 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     *h_passes = 0;
     if (h_rec_pass_off && rec_pass_cap > 0) h_rec_pass_off[0] = 0;
     if (h_rec_clause_off && rec_clause_cap > 0) h_rec_clause_off[0] = 0;
+    if (bad) return fail_arg("satmi_resolution_host", bad);
     // dense variable index (variables sorted by id)
-    const int64_t L = nclauses > 0 ? h_clause_off[nclauses] : 0;
-    int maxvar = 0;
+    const int64_t L = sh.Ltot;
+    const int maxvar = sh.max_var;
     std::vector<int32_t> var2dense, dense2var;
-    SATMI_TRY(dense_var_index("satmi_resolution_host", h_lits, L, &maxvar, &var2dense, &dense2var));
+    dense_var_index(h_lits, sh.L0, L, maxvar, &var2dense, &dense2var);
     const int V = (int)dense2var.size();
     const int W = std::max(1, (V + 63) / 64);
     const int K = 2 * W;
@@ -1123,9 +1125,10 @@ extern "C" int satmi_resolution_host(int nclauses, const int32_t *h_clause_off, 
     DevBuf &clauses = wk->clauses, &cand = wk->cand, &counters = wk->counters;
     // the clause offsets, the literals and the variable map in one pinned
     // staging buffer, sent in one copy
-    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_lits = al(4 * (size_t)(nclauses + 1)), o_map = o_lits + al(4 * (size_t)std::max<int64_t>(L, 1));
-    const size_t up_bytes = o_map + al(4 * (size_t)(maxvar + 1));
+    Carve cv;
+    cv.take(4 * (size_t)(nclauses + 1));
+    const size_t o_lits = cv.take(4 * (size_t)std::max<int64_t>(L, 1)), o_map = cv.take(4 * (size_t)(maxvar + 1));
+    const size_t up_bytes = cv.at;
     SATMI_TRY(wk->up.reserve(up_bytes, &RES_OOM));
     SATMI_TRY(wk->up_h.reserve(up_bytes));
     int64_t ncl = nclauses;

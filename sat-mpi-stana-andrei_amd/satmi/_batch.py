@@ -1,5 +1,5 @@
-"""What the resolution and Davis-Putnam wrappers share on the way into
-libsatmi.so: a formula's CSR arrays, ctypes pointers, and a
+"""What the wrappers share on the way into libsatmi.so: ctypes pointers (all of
+them), and for resolution and Davis-Putnam a formula's CSR arrays and a
 batched call's packed input."""
 import ctypes
 import itertools

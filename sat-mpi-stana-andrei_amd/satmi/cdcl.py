@@ -10,6 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _capi
+from ._batch import _p
 from .cnf import pack
 
 CDCL_UNSAT, CDCL_SAT, CDCL_LIMIT, CDCL_ERROR, CDCL_FULL = 0, 1, -1, -2, -3
@@ -43,11 +44,9 @@ def cdcl_batch_packed(batch, max_iter=0, time_limit=0.0, learn_cap=0, arrays=Fal
     assign = np.zeros((B, nv), dtype=np.int32)
     stats = np.zeros((B, NSTATS), dtype=np.int64)
     vinc = np.zeros(B, dtype=np.float64)
-    P = ctypes.POINTER
-    i32 = lambda a: a.ctypes.data_as(P(ctypes.c_int32))   # noqa: E731
-    rc = L.satmi_cdcl_batch_host(B, i32(batch.inst_clause_begin), i32(batch.clause_lit_begin), i32(batch.lits),
-                                 int(max_iter), int(learn_cap), float(time_limit), i32(status), i32(alen), i32(assign),
-                                 nv, stats.ctypes.data_as(P(ctypes.c_int64)), vinc.ctypes.data_as(P(ctypes.c_double)))
+    rc = L.satmi_cdcl_batch_host(B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits),
+                                 int(max_iter), int(learn_cap), float(time_limit), _p(status), _p(alen), _p(assign),
+                                 nv, _p(stats, ctypes.c_int64), _p(vinc, ctypes.c_double))
     _capi.check(rc, "satmi_cdcl_batch_host")
     if arrays:
         return {"status": status, "assign_len": alen, "assign": assign, "stats": stats, "var_inc": vinc}

@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
+from ._batch import _p
 from .cnf import CnfBatch, pack
 
 
@@ -53,10 +54,6 @@ class DpllResult:
         return check_packed(batch, rows, self.sol_len, self.sol_lits)
 
 
-def _ptr(a, t=ctypes.c_int32):
-    return a.ctypes.data_as(ctypes.POINTER(t))
-
-
 def dpll_batch(batch, mode="sound", max_solutions=1, node_limit=0, time_limit=0.0, sol_cap=None,
                inits=None):
     """Run batched DPLL.  `batch` is a CnfBatch or a list of formulas; `inits`
@@ -90,10 +87,10 @@ def dpll_batch(batch, mode="sound", max_solutions=1, node_limit=0, time_limit=0.
     root_lits = np.zeros((B, stride), dtype=np.int32)
     m = {"ref": _capi.MODE_REF, "sound": _capi.MODE_SOUND}[mode]
     rc = L.satmi_dpll_batch_host(
-        B, _ptr(batch.inst_clause_begin), _ptr(batch.clause_lit_begin), _ptr(batch.lits),
-        _ptr(batch.inst_nvars), _ptr(init_begin) if init_begin is not None else None,
-        _ptr(init_lits) if init_lits is not None else None, m, int(max_solutions), int(node_limit),
-        float(time_limit), int(sol_cap), int(stride), _ptr(status), _ptr(counters, ctypes.c_int64),
-        _ptr(sol_len), _ptr(sol_lits), _ptr(root_len), _ptr(root_lits))
+        B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits),
+        _p(batch.inst_nvars), _p(init_begin) if init_begin is not None else None,
+        _p(init_lits) if init_lits is not None else None, m, int(max_solutions), int(node_limit),
+        float(time_limit), int(sol_cap), int(stride), _p(status), _p(counters, ctypes.c_int64),
+        _p(sol_len), _p(sol_lits), _p(root_len), _p(root_lits))
     _capi.check(rc, "satmi_dpll_batch_host")
     return DpllResult(status, counters, sol_len, sol_lits, root_len, root_lits)

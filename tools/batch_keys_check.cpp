@@ -7,7 +7,10 @@
 // the naive side is a std::map from variable id to rank and one bit per
 // literal.  Every key is decoded back and compared with the clause's literal
 // set in the decoder's order, and every message of the CSR check is provoked.
-// Exit status 1 on the first mismatch.
+// The shape the check measures (CsrShape, nvars) is held to a restatement over
+// the formulas themselves: on every batch above, on every formula of them as a
+// batch of one, and on the batches laid out as a window into larger arrays
+// (icb[0] > 0, clb[0] > 0).  Exit status 1 on the first mismatch.
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -33,9 +36,17 @@ static int g_checks = 0;
         }                                                   \
     } while (0)
 
+// `fs` in CSR form; as a window: behind `pad` literals that belong to no clause
+// (zeros: never read) and the clauses `pre` that belong to no formula
 struct Csr {
-    std::vector<int32_t> icb{0}, clb{0}, lits;
-    explicit Csr(const std::vector<Formula> &fs) {
+    std::vector<int32_t> icb, clb, lits;
+    explicit Csr(const std::vector<Formula> &fs, const Formula &pre = {}, size_t pad = 0) : lits(pad, 0) {
+        clb.push_back((int32_t)pad);
+        for (const auto &c : pre) {
+            lits.insert(lits.end(), c.begin(), c.end());
+            clb.push_back((int32_t)lits.size());
+        }
+        icb.push_back((int32_t)pre.size());
         for (const Formula &f : fs) {
             for (const auto &c : f) {
                 lits.insert(lits.end(), c.begin(), c.end());
@@ -92,10 +103,81 @@ static Formula draw_formula(std::mt19937_64 &rng, const std::vector<int32_t> &id
     return f;
 }
 
+static uint32_t mag(int32_t l) { return l < 0 ? 0u - (uint32_t)l : (uint32_t)l; }
+
+// The shape of `fs` behind `pad` literals and the clauses `pre`, restated over
+// the formulas: clause by clause, literal by literal
+static CsrShape naive_shape(const std::vector<Formula> &fs, const Formula &pre, size_t pad, std::vector<int32_t> *nvars) {
+    CsrShape n;
+    n.L0 = n.Ltot = (int64_t)pad;
+    const auto clause = [&](const std::vector<int32_t> &c) {
+        uint32_t m = 0;
+        for (int32_t l : c) m = std::max(m, mag(l));
+        ++n.C;
+        n.Ltot += (int64_t)c.size();
+        n.max_len = std::max(n.max_len, (int)c.size());
+        n.min_len = std::min(n.min_len, (int)c.size());
+        n.max_var = std::max(n.max_var, (int)m);
+        return (int)m;
+    };
+    for (const auto &c : pre) clause(c);
+    nvars->clear();
+    for (const Formula &f : fs) {
+        int nv = 0, nl = 0;
+        for (const auto &c : f) nv = std::max(nv, clause(c)), nl += (int)c.size();
+        nvars->push_back(nv);
+        n.max_clauses = std::max(n.max_clauses, (int)f.size());
+        n.max_lits = std::max(n.max_lits, nl);
+    }
+    return n;
+}
+
+static void check_same_shape(const CsrShape &g, const CsrShape &n, const char *what, const char *form) {
+    CHECK(g.C == n.C && g.L0 == n.L0 && g.Ltot == n.Ltot, "%s (%s): C %d L0 %lld Ltot %lld, want %d %lld %lld", what,
+          form, g.C, (long long)g.L0, (long long)g.Ltot, n.C, (long long)n.L0, (long long)n.Ltot);
+    CHECK(g.max_clauses == n.max_clauses && g.max_lits == n.max_lits, "%s (%s): max_clauses %d max_lits %d, want %d %d",
+          what, form, g.max_clauses, g.max_lits, n.max_clauses, n.max_lits);
+    CHECK(g.max_len == n.max_len && g.min_len == n.min_len, "%s (%s): max_len %d min_len %d, want %d %d", what, form,
+          g.max_len, g.min_len, n.max_len, n.min_len);
+    CHECK(g.max_var == n.max_var, "%s (%s): max_var %d, want %d", what, form, g.max_var, n.max_var);
+}
+
+// The shape and every nvars[b] of a good batch, with and without nvars asked
+// for, in the layout given; at offset 0 every formula as a batch of one besides
+static void check_shape(const std::vector<Formula> &fs, const char *what, const Formula &pre = {}, size_t pad = 0) {
+    const Csr a(fs, pre, pad);
+    const int B = (int)fs.size();
+    std::vector<int32_t> want_nv, nv((size_t)B, -7);
+    const CsrShape want = naive_shape(fs, pre, pad, &want_nv);
+    CsrShape got;
+    got.C = -7;   // (an empty batch's shape is written too)
+    CHECK(batch_csr_check(B, a.icb.data(), a.clb.data(), a.lits.data(), nullptr, true, &got) == nullptr,
+          "%s: a good batch is refused (shape)", what);
+    check_same_shape(got, B ? want : CsrShape{}, what, "shape");
+    CHECK(batch_csr_check(B, a.icb.data(), a.clb.data(), a.lits.data(), nullptr, true, &got, nv.data()) == nullptr,
+          "%s: a good batch is refused (shape, nvars)", what);
+    check_same_shape(got, B ? want : CsrShape{}, what, "shape, nvars");
+    for (int b = 0; b < B; ++b)
+        CHECK(nv[(size_t)b] == want_nv[(size_t)b], "%s: formula %d: largest variable %d, want %d", what, b,
+              nv[(size_t)b], want_nv[(size_t)b]);
+    if (!pre.empty() || pad) return;
+    for (int b = 0; b < B; ++b) {   // clause_off is the formula's slice of clb, rebased
+        const Csr one({fs[(size_t)b]});
+        std::vector<int32_t> one_nv;
+        const CsrShape w1 = naive_shape({fs[(size_t)b]}, {}, 0, &one_nv);
+        CHECK(formula_csr_check((int)fs[(size_t)b].size(), one.clb.data(), one.lits.data(), nullptr, true, &got) == nullptr,
+              "%s: formula %d alone is refused", what, b);
+        check_same_shape(got, w1, what, "batch of one");
+        CHECK(got.max_var == one_nv[0] && got.max_clauses == got.C && got.max_lits == got.Ltot,
+              "%s: formula %d alone: its shape is not the formula's", what, b);
+    }
+}
+
 static void check_batch(const std::vector<Formula> &fs, const char *what) {
     const Csr a(fs);
     const int B = (int)fs.size();
     CHECK(batch_csr_check(B, a.icb.data(), a.clb.data(), a.lits.data()) == nullptr, "%s: a good batch is refused", what);
+    check_shape(fs, what);
     BatchKeys K;
     batch_encode(B, a.icb.data(), a.clb.data(), a.lits.data(), &K);
     const size_t C = a.clb.size() - 1;
@@ -160,6 +242,40 @@ static void check_named() {
     check_batch({{{1}}, huge, {{-2}}}, "more than 2^20 variables");
 }
 
+static void check_shapes() {
+    const Formula six = {{}, {1, -2, 3, -4, 5, -6}}, two = {{7, -8}, {9}}, pre = {{40, -41, 42}, {}, {-43}};
+    check_shape({six}, "an empty clause beside a six-literal clause");
+    {
+        CsrShape sh;
+        const Csr a({two, six});
+        CHECK(batch_csr_check(2, a.icb.data(), a.clb.data(), a.lits.data(), nullptr, true, &sh) == nullptr &&
+                  sh.min_len == 0 && sh.max_len == 6,
+              "min_len 0 and max_len 6");
+    }
+    check_shape({{}, two, six}, "an empty formula first");
+    check_shape({two, {}, six}, "an empty formula in the middle");
+    check_shape({two, six, {}}, "an empty formula last");
+    check_shape({{}, {}}, "no clause at all");
+    // windows into larger arrays: clb[0] > 0, icb[0] > 0, both; the clauses
+    // before the first formula's count for max_len, min_len and max_var only
+    check_shape({two, {}, six}, "window: clb[0] > 0", {}, 5);
+    check_shape({two, {}, six}, "window: icb[0] > 0", pre, 0);
+    check_shape({two, {}, six}, "window: icb[0] > 0 and clb[0] > 0", pre, 5);
+    check_shape({{}, two}, "window: an empty formula first", pre, 3);
+    check_shape({two}, "window: a longer clause before the window", {{1, 2, 3, 4, 5, 6, 7, -99}}, 1);
+    {   // the batch of one reads neither array without clauses, and names its count
+        CsrShape sh;
+        CHECK(formula_csr_check(0, nullptr, nullptr, nullptr, true, &sh) == nullptr && sh.C == 0 && sh.Ltot == 0,
+              "a formula without clauses");
+        const int32_t off[2] = {0, 1}, lit[1] = {5};
+        CHECK(!std::strcmp(formula_csr_check(-1, off, lit, "own", true, &sh), "negative clause count"), "formula: count");
+        CHECK(!std::strcmp(formula_csr_check(1, off, lit, "own", true, &sh), "own"), "formula: own");
+        CHECK(!std::strcmp(formula_csr_check(1, nullptr, lit, nullptr, true, &sh), "null pointer"), "formula: clause_off");
+        CHECK(!std::strcmp(formula_csr_check(1, off, nullptr, nullptr, true, &sh), "null pointer"), "formula: lits");
+        CHECK(!std::strcmp(formula_csr_check(1, off, lit, nullptr, false, &sh), "null pointer"), "formula: outputs");
+    }
+}
+
 static void check_random() {
     for (uint64_t seed = 1; seed <= 200; ++seed) {
         std::mt19937_64 rng(seed);
@@ -178,6 +294,7 @@ static void check_random() {
         char what[32];
         std::snprintf(what, sizeof what, "seed %llu", (unsigned long long)seed);
         check_batch(fs, what);
+        check_shape(fs, what, draw_formula(rng, draw_ids(rng, 1 + (int)(rng() % 40), rng() % 2)), rng() % 9);
     }
 }
 
@@ -188,6 +305,8 @@ static void check_messages() {
     const Csr good(fs);
     const int B = 3;
     const int32_t *icb = good.icb.data(), *clb = good.clb.data(), *lits = good.lits.data();
+    CsrShape sh;   // the same messages with the shape and nvars asked for
+    int32_t nv[3];
     CHECK(is(batch_csr_check(B, icb, clb, lits), nullptr), "good");
     CHECK(is(batch_csr_check(-1, icb, clb, lits), "negative formula count"), "count");
     // the caller's own complaint ranks behind the count and before everything else
@@ -208,17 +327,23 @@ static void check_messages() {
         Csr x(fs);
         x.icb[(size_t)at] = at == 0 ? -1 : x.icb[(size_t)at - 1] - 1;
         CHECK(is(batch_csr_check(B, x.icb.data(), clb, lits), "clause ranges are not ascending"), "icb[%d]", at);
+        CHECK(is(batch_csr_check(B, x.icb.data(), clb, lits, nullptr, true, &sh, nv), "clause ranges are not ascending"),
+              "icb[%d] (shape)", at);
     }
     for (int at : {0, 2, 3}) {
         Csr x(fs);
         x.clb[(size_t)at] = at == 0 ? -1 : x.clb[(size_t)at - 1] - 1;
         CHECK(is(batch_csr_check(B, icb, x.clb.data(), lits), "literal ranges are not ascending"), "clb[%d]", at);
+        CHECK(is(batch_csr_check(B, icb, x.clb.data(), lits, nullptr, true, &sh, nv), "literal ranges are not ascending"),
+              "clb[%d] (shape)", at);
     }
     for (int32_t bad : {0, INT32_MIN})
         for (size_t at : {(size_t)0, good.lits.size() - 1}) {
             Csr x(fs);
             x.lits[at] = bad;
             CHECK(is(batch_csr_check(B, icb, clb, x.lits.data()), "literal 0 / INT32_MIN"), "literal %d", (int)bad);
+            CHECK(batch_csr_check(B, icb, clb, x.lits.data(), nullptr, true, &sh, nv) == CSR_BAD_LITERAL,
+                  "literal %d (shape)", (int)bad);
         }
     // the order among them: ranges before literals, clause ranges before literal ranges
     Csr x(fs);
@@ -232,6 +357,7 @@ static void check_messages() {
 int main() {
     check_messages();
     check_named();
+    check_shapes();
     check_random();
     std::printf("batch_keys_check: ok (%d checks)\n", g_checks);
     return 0;
