@@ -413,7 +413,7 @@ int satmi_cdcl_last_stats(double *span_s, double *busy_wave_s, int *resident_wav
  * length outside 0 .. stride is SATMI_ERR_ARG), computes max_vars over the
  * formulas and the rows and max_clause_len itself, and is thread-safe: a call
  * leases a workspace with its own stream, like satmi_resolution_batch_host.
- * UNSAT answers get no certificate here.
+ * UNSAT answers are certified by satmi_check_refutations_* below.
  */
 #define SATMI_CHECK_NWORDS 4          /* per row: falsified, undetermined, first_falsified (-1: none), flags */
 #define SATMI_CHECK_CONTRADICTORY 1   /* flags bit: some v with both +v and -v in the row */
@@ -431,6 +431,69 @@ int satmi_check_models_host(int num_instances, const int32_t *h_inst_clause_begi
  * are launched, of `waves_per_wg` (1, 2 or 4) wavefronts each, so a few dozen
  * tiny instances exercise table reuse across instances and every region layout. */
 int satmi_check_debug_grid(int workgroups, int waves_per_wg);
+
+/*
+ * Batched refutation check: verifies UNSAT answers by forward reverse unit
+ * propagation (RUP), one wavefront per instance (csrc/refute.hip).  Instance b
+ * has the formula F of the CSR arrays above and the ordered lemma clauses
+ * L0 .. Lk-1 of a second CSR triple of the same shape: its lemmas are
+ * proof_inst_begin[b] .. proof_inst_begin[b + 1], lemma p's literals
+ * proof_clause_begin[p] .. proof_clause_begin[p + 1] of proof_lits.
+ *   Lemma Li is VERIFIED if assigning every literal of Li false and running
+ *   unit propagation to a fixpoint over F and L0 .. Li-1 reaches a conflict: a
+ *   clause whose literals are all false (the empty clause always is), or a
+ *   variable needed with both signs.  An earlier lemma is a premise whether or
+ *   not it verified: a verdict means "follows by unit propagation from F and
+ *   the lemmas before it".  A lemma that holds +v and -v is verified trivially
+ *   and sets SATMI_REFUTE_TAUTOLOGY; a repeated literal counts once.  Checking
+ *   ends with the instance's first empty lemma, which is checked like any
+ *   other; the lemmas behind it are not checked.  Unit propagation is confluent
+ *   about reaching a conflict, so every output is independent of scan order.
+ *   The record of satmi_resolution_host / satmi_resolution_batch_host (the
+ *   clauses each pass added) or of satmi_dp_host / satmi_dp_batch_host (the
+ *   clause list after each step), in order, followed by the empty clause when
+ *   the result was 0, is such a proof: every recorded clause is a resolvent of
+ *   two clauses before it, and the empty one of two opposite unit clauses.
+ *   max_vars       the truth table and the trail of assigned variables hold
+ *                  variables 1 .. max_vars in the wavefront's LDS; at most
+ *                  SATMI_REFUTE_MAX_VARS (8 KiB + 64 KiB), beyond which the call
+ *                  returns SATMI_ERR_TOO_LARGE before any launch.  A literal 0,
+ *                  INT32_MIN or with |l| > max_vars sets SATMI_REFUTE_BAD_LITERAL:
+ *                  a formula clause or an earlier lemma that holds one is
+ *                  skipped as a premise (sound), a lemma that holds one fails.
+ *   max_clause_len longest clause of formulas and lemmas, 0 = unknown: 1 .. 8
+ *                  takes the lane-per-clause form, anything else the
+ *                  wave-per-clause form (same results)
+ *   out            [B x SATMI_REFUTE_NWORDS]: status, checked lemmas that
+ *                  failed, index of the first failed lemma relative to the
+ *                  instance's first lemma (-1: none), flags
+ *   lemma_ok       [P = proof_inst_begin[B]] or NULL: 1 verified, 0 failed,
+ *                  -1 not checked
+ * The device form is asynchronous on `stream` (NULL = default stream) and owns
+ * no device memory.  The host form checks both triples before any HIP call
+ * (num_instances == 0 returns SATMI_OK; a literal 0 / INT32_MIN is
+ * SATMI_ERR_ARG), computes max_vars and max_clause_len itself, and is
+ * thread-safe: a call leases a workspace with its own stream.
+ */
+#define SATMI_REFUTE_NWORDS 4         /* per instance: status, failed, first_failed (-1: none), flags */
+#define SATMI_REFUTE_FAILED 0         /* status: at least one checked lemma failed */
+#define SATMI_REFUTE_PROVEN 1         /* status: no checked lemma failed and an empty lemma was reached */
+#define SATMI_REFUTE_OPEN 2           /* status: none failed, no empty lemma reached (an empty proof) */
+#define SATMI_REFUTE_TAUTOLOGY 1      /* flags bit: a checked lemma holds both +v and -v */
+#define SATMI_REFUTE_BAD_LITERAL 2    /* flags bit: a literal 0, INT32_MIN or |l| > max_vars in the formula or a checked lemma */
+#define SATMI_REFUTE_MAX_VARS 32767   /* the largest max_vars: a trail entry is 16 bits */
+int satmi_check_refutations_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                   const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                   const int32_t *d_proof_inst_begin, const int32_t *d_proof_clause_begin,
+                                   const int32_t *d_proof_lits, int max_vars, int max_clause_len, int32_t *d_out,
+                                   int32_t *d_lemma_ok, void *stream);
+int satmi_check_refutations_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                 const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                 const int32_t *h_proof_inst_begin, const int32_t *h_proof_clause_begin,
+                                 const int32_t *h_proof_lits, int32_t *h_out, int32_t *h_lemma_ok);
+
+/* Test knob of the refutation check, as satmi_check_debug_grid. */
+int satmi_refute_debug_grid(int workgroups, int waves_per_wg);
 
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into

@@ -31,6 +31,12 @@ CHECK_NWORDS = 4
 CHECK_WORDS = ("falsified", "undetermined", "first_falsified", "flags")
 CHECK_CONTRADICTORY, CHECK_BAD_LITERAL = 1, 2
 CHECK_MAX_VARS = 524287
+# satmi_check_refutations_*: words per instance, their names, the statuses, the flags bits, the largest max_vars
+REFUTE_NWORDS = 4
+REFUTE_WORDS = ("status", "failed", "first_failed", "flags")
+REFUTE_FAILED, REFUTE_PROVEN, REFUTE_OPEN = 0, 1, 2
+REFUTE_TAUTOLOGY, REFUTE_BAD_LITERAL = 1, 2
+REFUTE_MAX_VARS = 32767
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
 EXPORTED = (
@@ -47,6 +53,7 @@ EXPORTED = (
     "satmi_resolution_batch_host", "satmi_resolution_debug_batch",
     "satmi_dp_batch_host", "satmi_dp_debug_batch",
     "satmi_check_models_device", "satmi_check_models_host", "satmi_check_debug_grid",
+    "satmi_check_refutations_device", "satmi_check_refutations_host", "satmi_refute_debug_grid",
 )
 
 
@@ -177,6 +184,10 @@ def load():
     L.satmi_check_models_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, i32p, i32p, i32p,
                                           ctypes.c_int, ctypes.c_int, i32p]
     L.satmi_check_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.satmi_check_refutations_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int,
+                                                 vp, vp, vp]
+    L.satmi_check_refutations_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]
+    L.satmi_refute_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = library/header mismatch
     _lib = L

@@ -8,7 +8,7 @@ the check returns _capi.CHECK_WORDS: clauses falsified, clauses undetermined,
 the index of the first falsified clause (-1: none) and flags
 (CHECK_CONTRADICTORY: some v with +v and -v in the row; CHECK_BAD_LITERAL: a
 literal 0 or beyond the table, ignored).  A row is a model iff words 0, 1 and 3
-are all 0.  UNSAT answers get no certificate here.
+are all 0.  UNSAT answers are certified by satmi/refute.py (check_refutations).
 """
 import numpy as np
 

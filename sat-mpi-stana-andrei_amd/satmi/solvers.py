@@ -97,6 +97,15 @@ def check_assignment(formula: Formula, assignment) -> bool:
     return check_models([formula], [[assignment]])[0][0]["ok"]
 
 
+def check_refutation(formula: Formula, proof) -> bool:
+    """Whether `proof` (an ordered list of lemma clauses that reaches the empty clause, e.g.
+    refute.proof_of_resolution of a recorded False answer) refutes `formula`, checked on the
+    GPU (satmi/refute.py): every lemma up to the first empty one follows by unit propagation
+    from the formula and the lemmas before it."""
+    from .refute import check_refutations
+    return check_refutations([formula], [proof])[0]["proven"]
+
+
 def resolution_solver(formula: Formula) -> bool:
     from .resolution import resolution_solve
     return resolution_solve(formula, time_limit=_time_limit)
