@@ -144,7 +144,7 @@ def run_traced(fn_name, formula, seconds, *args):
 
     f_copy = [list(c) for c in formula]
     signal.signal(signal.SIGALRM, _alarm)
-    signal.setitimer(signal.ITIMER_REAL, seconds)
+    signal.setitimer(signal.ITIMER_REAL, seconds, 1.0)   # again every second: a raise that lands where CPython drops it must not leave the run unbounded
     sys.settrace(global_tracer)
     try:
         result = fn(f_copy, *args)

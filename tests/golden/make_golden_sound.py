@@ -141,8 +141,17 @@ def _alarm(signum, frame):
     raise Timeout()
 
 
-def run_sound(formula, seconds):
-    """Run the rewritten reference DPLL on `formula`; returns the observation."""
+class _First(Exception):
+    pass
+
+
+def run_sound(formula, seconds, init=None, sol_cap=0, first_only=False):
+    """Run the rewritten reference DPLL on `formula`; returns the observation.
+    `init`: a caller's assignment dict, passed as the reference's second
+    argument (the dict as the call leaves it is recorded as "init_after");
+    `sol_cap` > 0: the first sol_cap solutions of a finished enumeration are
+    kept, each in its dict order; `first_only`: the run is stopped by the
+    observer at the first `return [assignment]`."""
     ctr = {"nodes": 0, "unit_raw": 0, "pure_assigns": 0, "decisions": 0, "conflicts": 0}
     first = {}
     pending = [0]   # decision children whose first unit assignment is still to come
@@ -172,6 +181,8 @@ def run_sound(formula, seconds):
         elif ln in L_SOL and frame.f_code is CODE and not first:
             first["counters"] = snapshot()
             first["model"] = [v if b else -v for v, b in frame.f_locals["assignment"].items()]
+            if first_only:
+                raise _First()
         return local
 
     def glob(frame, event, arg):
@@ -186,13 +197,14 @@ def run_sound(formula, seconds):
         return None
 
     f_copy = [list(c) for c in formula]
+    args = () if init is None else (init,)
     signal.signal(signal.SIGALRM, _alarm)
-    signal.setitimer(signal.ITIMER_REAL, seconds)
+    signal.setitimer(signal.ITIMER_REAL, seconds, 1.0)   # again every second: a raise that lands where CPython drops it must not leave the run unbounded
     sys.settrace(glob)
     done = True
     try:
-        res = NS["dpll_optimized"](f_copy)
-    except Timeout:
+        res = NS["dpll_optimized"](f_copy, *args)
+    except (Timeout, _First):
         done = False
         res = None
     finally:
@@ -206,6 +218,10 @@ def run_sound(formula, seconds):
     if done:
         case["full"] = {"counters": snapshot(), "solutions": len(res),
                         "first_solution": ([v if b else -v for v, b in res[0].items()] if res else None)}
+        if sol_cap > 0:
+            case["full"]["solution_list"] = [[v if b else -v for v, b in s.items()] for s in res[:sol_cap]]
+        if init is not None:
+            case["init_after"] = [v if b else -v for v, b in init.items()]
     return case
 
 

@@ -4,13 +4,13 @@ single-call path: verdicts, per-pass counts and the exact clause set of every
 pass; workgroup reuse, the capacity (UNFIT) contract, the limits, the record's
 truncation and concurrent calls."""
 import ctypes
-import random
 import threading
 
 import numpy as np
 import pytest
 
 import oracle
+import res_batch_rows
 from satmi import _capi, cnf
 from satmi import resolution as res_mod
 from satmi.resolution import debug_batch, resolve, resolve_batch
@@ -34,20 +34,10 @@ def _same(r, o, what=None):
 
 @pytest.fixture(scope="module")
 def mix():
-    """200 formulas drawn as test_resolution_gpu.py::test_matches_oracle_random draws
-    its 60, their oracle results and one recorded batch run of them all."""
-    rng = random.Random(17)
-    fs = []
-    for it in range(200):
-        n = rng.randint(2, 7)
-        m = rng.randint(1, 12)
-        f = [[v if rng.random() < 0.5 else -v for v in rng.sample(range(1, n + 1), rng.randint(1, min(3, n)))]
-             for _ in range(m)]
-        if it % 7 == 0:
-            f.append(list(f[0]))                      # duplicate clause
-        if it % 11 == 0:
-            f.append([1, -1, 2][:min(3, n + 1)])      # tautological input clause
-        fs.append(f)
+    """The 200 formulas of tests/res_batch_rows.py (drawn as
+    test_resolution_gpu.py::test_matches_oracle_random draws its 60), their
+    oracle results and one recorded batch run of them all."""
+    fs = res_batch_rows.mix()
     want = [oracle.resolution(f, record=True) for f in fs]
     got = resolve_batch(fs, record=True)
     return fs, want, got
@@ -59,7 +49,7 @@ def bench_set():
 
 
 def test_edge_cases_in_one_batch():
-    fs = [[], [[]], [[1]], [[1], [-1]], [[1, -1]], [[1, 1], [-1]], [[1, 2], [], [-1]], [[1, -1], [1, -1]]]
+    fs = res_batch_rows.EDGE
     got = resolve_batch(fs)
     assert [r["result"] for r in got[:7]] == [1, 1, 1, 0, 1, 0, 1]
     for f, r in zip(fs, got):
