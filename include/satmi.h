@@ -495,6 +495,73 @@ int satmi_check_refutations_host(int num_instances, const int32_t *h_inst_clause
 /* Test knob of the refutation check, as satmi_check_debug_grid. */
 int satmi_refute_debug_grid(int workgroups, int waves_per_wg);
 
+/*
+ * Batched refutation trimming: the backward form of the check above, one
+ * wavefront per instance (csrc/trim.hip).  The instances are given as for
+ * satmi_check_refutations_*.  Besides a verdict it answers which formula
+ * clauses make the formula unsatisfiable (the core) and which lemmas the
+ * refutation needs (the trimmed proof).
+ *   Let e be the instance's first empty lemma; with none the status is
+ *   SATMI_REFUTE_OPEN and nothing is marked.  The lemmas behind e are never
+ *   looked at.  Le is marked needed, and i runs e, e-1, .., 0: a lemma that is
+ *   not needed is skipped; a needed lemma is checked exactly as the forward
+ *   check does it (its literals false, unit propagation over F and L0 .. Li-1,
+ *   an earlier lemma a premise whether or not it would verify, a clause with a
+ *   bad literal no premise, a needed lemma with a bad literal failed, a
+ *   tautological one verified), and every propagated literal remembers the
+ *   clause that made it unit.  On a conflict the falsified clause (or the two
+ *   clauses that need one variable with both signs) is marked, and,
+ *   transitively, the reason of every false literal of a marked clause: a
+ *   marked formula clause is in the core, a marked lemma becomes needed.  A
+ *   tautological lemma marks nothing.  A needed lemma that reaches no conflict
+ *   has failed, marks nothing, and the walk goes on.
+ *   The status is SATMI_REFUTE_FAILED if a needed lemma failed, else
+ *   SATMI_REFUTE_PROVEN: the core clauses alone, with the needed lemmas in
+ *   their order, are a proof that satmi_check_refutations_* accepts with no
+ *   failed lemma.  That is weaker than the forward PROVEN: a lemma that does
+ *   not verify but that nothing needs does not count.  Where the forward check
+ *   reports no failed lemma and reaches an empty lemma, the trim is PROVEN.
+ *   Which core is found depends on the propagation order, so the marks are a
+ *   function of the inputs and of the clause form (max_clause_len below), and
+ *   of nothing else; the two forms may return different, equally valid cores.
+ *   max_vars       as above, at most SATMI_TRIM_MAX_VARS: the wavefront's LDS
+ *                  holds the truth table, a bitmap of the analysis, the trail
+ *                  and a 32-bit reason per trail entry (4 + 2 + 32 + 64 KiB at
+ *                  the limit); beyond it the call returns SATMI_ERR_TOO_LARGE
+ *                  before any launch
+ *   max_clause_len as above: 1 .. 8 the lane-per-clause form, else wave-per-clause
+ *   out            [B x SATMI_TRIM_NWORDS]: status, needed lemmas that failed,
+ *                  the lowest index of a failed needed lemma (-1: none), flags
+ *                  (SATMI_REFUTE_BAD_LITERAL for the formula and the needed
+ *                  lemmas, SATMI_REFUTE_TAUTOLOGY for the needed lemmas), the
+ *                  number of core clauses (marks that are 1), the number of
+ *                  needed lemmas (marks that are not -1)
+ *   core           [C = inst_clause_begin[B]]: 1 in the core, 0 not
+ *   lemma          [P = proof_inst_begin[B]]: 1 needed and verified, 0 needed
+ *                  and failed, -1 not needed
+ * The device form is asynchronous on `stream`, owns no device memory and needs
+ * no memset: the kernel initialises its instances' ranges of both mark arrays,
+ * which are the walk's own state, so neither pointer may be NULL there.  The
+ * host form checks both triples before any HIP call, as the forward check's
+ * does and with its messages; either of its mark pointers may be NULL; clauses
+ * and lemmas before the first instance's ranges read 0 / -1.  It is
+ * thread-safe: a call leases a workspace with its own stream.
+ */
+#define SATMI_TRIM_NWORDS 6           /* per instance: status, failed, first_failed (-1: none), flags, core clauses, kept lemmas */
+#define SATMI_TRIM_MAX_VARS 16383     /* the largest max_vars: a 102 KiB region in a CU's 160 KiB */
+int satmi_trim_refutations_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                  const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                  const int32_t *d_proof_inst_begin, const int32_t *d_proof_clause_begin,
+                                  const int32_t *d_proof_lits, int max_vars, int max_clause_len, int32_t *d_out,
+                                  int32_t *d_core, int32_t *d_lemma, void *stream);
+int satmi_trim_refutations_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                const int32_t *h_proof_inst_begin, const int32_t *h_proof_clause_begin,
+                                const int32_t *h_proof_lits, int32_t *h_out, int32_t *h_core, int32_t *h_lemma);
+
+/* Test knob of the trim, as satmi_check_debug_grid. */
+int satmi_trim_debug_grid(int workgroups, int waves_per_wg);
+
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into
  * d_span: [0] = ~(first wave's start), [1] = last wave's end, so the launch

@@ -37,6 +37,10 @@ REFUTE_WORDS = ("status", "failed", "first_failed", "flags")
 REFUTE_FAILED, REFUTE_PROVEN, REFUTE_OPEN = 0, 1, 2
 REFUTE_TAUTOLOGY, REFUTE_BAD_LITERAL = 1, 2
 REFUTE_MAX_VARS = 32767
+# satmi_trim_refutations_*: words per instance, their names (statuses and flags bits are REFUTE_*), the largest max_vars
+TRIM_NWORDS = 6
+TRIM_WORDS = ("status", "failed", "first_failed", "flags", "core_clauses", "kept_lemmas")
+TRIM_MAX_VARS = 16383
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
 EXPORTED = (
@@ -54,6 +58,7 @@ EXPORTED = (
     "satmi_dp_batch_host", "satmi_dp_debug_batch",
     "satmi_check_models_device", "satmi_check_models_host", "satmi_check_debug_grid",
     "satmi_check_refutations_device", "satmi_check_refutations_host", "satmi_refute_debug_grid",
+    "satmi_trim_refutations_device", "satmi_trim_refutations_host", "satmi_trim_debug_grid",
 )
 
 
@@ -188,6 +193,10 @@ def load():
                                                  vp, vp, vp]
     L.satmi_check_refutations_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]
     L.satmi_refute_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.satmi_trim_refutations_device.argtypes = [ctypes.c_int, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_int,
+                                                vp, vp, vp, vp]
+    L.satmi_trim_refutations_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]
+    L.satmi_trim_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = library/header mismatch
     _lib = L

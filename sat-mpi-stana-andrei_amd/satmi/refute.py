@@ -16,6 +16,10 @@ The records of resolve / resolve_batch and eliminate / eliminate_batch are such
 proofs (proof_of_resolution, proof_of_elimination): every recorded clause is a
 resolvent of two clauses before it, and the empty clause that ends a False
 answer comes from two opposite unit clauses.
+
+trim_refutations (csrc/trim.hip) is the backward form: from the first empty lemma
+downwards it checks only the lemmas that lemma needs, and returns which formula
+clauses (the UNSAT core) and which lemmas (the trimmed proof) the refutation uses.
 """
 import numpy as np
 
@@ -75,6 +79,64 @@ def check_refutations_device(num_instances, icb, clb, lits, proof_icb, proof_clb
                                                      proof_lits, int(max_vars), int(max_clause_len), out, lemma_ok,
                                                      stream)
     _capi.check(rc, "satmi_check_refutations_device")
+
+
+# ---- the backward form: UNSAT cores and trimmed proofs (csrc/trim.hip)
+def trim_debug_grid(workgroups=0, waves_per_wg=0):
+    """debug_grid for the trim's launches."""
+    _capi.check(_capi.load().satmi_trim_debug_grid(int(workgroups), int(waves_per_wg)), "satmi_trim_debug_grid")
+
+
+def trim_refutations_packed(batch, proof_batch):
+    """satmi_trim_refutations_host on two CnfBatches, as check_refutations_packed.  Returns
+    (int32 [B, 6] words, int32 [C] core marks: 1 / 0 per formula clause, int32 [P] lemma marks:
+    1 needed and verified, 0 needed and failed, -1 not needed)."""
+    B = batch.num_instances
+    if proof_batch.num_instances != B:
+        raise ValueError("proofs must have one list of lemmas per formula")
+    out = np.zeros((B, _capi.TRIM_NWORDS), dtype=np.int32)
+    core = np.zeros(int(batch.inst_clause_begin[B]) if B else 0, dtype=np.int32)
+    lemma = np.full(int(proof_batch.inst_clause_begin[B]) if B else 0, -1, dtype=np.int32)
+    if B:
+        f, p = _csr(batch), _csr(proof_batch)
+        rc = _capi.load().satmi_trim_refutations_host(B, *map(_p, f), *map(_p, p), _p(out),
+                                                      _p(core) if core.size else None,
+                                                      _p(lemma) if lemma.size else None)
+        _capi.check(rc, "satmi_trim_refutations_host")
+    return out, core, lemma
+
+
+def trim_refutations(formulas_or_batch, proofs):
+    """Trim `proofs[b]` against formula b by the backward check: only the lemmas that the
+    first empty lemma needs are checked, and what they use is marked.  Returns one dict per
+    formula: status, failed, first_failed, flags, proven (status == REFUTE_PROVEN: the core
+    clauses with the kept lemmas are a proof check_refutations accepts), "core": ascending
+    clause indices into the formula, "kept": ascending lemma indices (the ending empty lemma
+    included), "proof": the kept lemma clauses, in order.  Which core is found depends on the
+    clause form the launch takes (satmi.h), never on anything else."""
+    batch = formulas_or_batch if isinstance(formulas_or_batch, CnfBatch) else pack(formulas_or_batch)
+    proof_batch = proofs if isinstance(proofs, CnfBatch) else pack(proofs)
+    out, core, lemma = trim_refutations_packed(batch, proof_batch)
+    icb, pib = batch.inst_clause_begin, proof_batch.inst_clause_begin
+    res = []
+    for b, w in enumerate(out):
+        r = dict(zip(_capi.REFUTE_WORDS, map(int, w[:4])), proven=bool(w[0] == _capi.REFUTE_PROVEN))
+        r["core"] = np.flatnonzero(core[icb[b]:icb[b + 1]] == 1).tolist()
+        r["kept"] = np.flatnonzero(lemma[pib[b]:pib[b + 1]] >= 0).tolist()
+        lemmas = proof_batch.instance(b)
+        r["proof"] = [list(lemmas[j]) for j in r["kept"]]
+        res.append(r)
+    return res
+
+
+def trim_refutations_device(num_instances, icb, clb, lits, proof_icb, proof_clb, proof_lits, max_vars,
+                            max_clause_len, out, core, lemma, stream=None):
+    """satmi_trim_refutations_device on device pointers (ints, e.g. a tensor's data_ptr());
+    asynchronous on `stream`.  `core` and `lemma` are both required and need no initialisation."""
+    rc = _capi.load().satmi_trim_refutations_device(int(num_instances), icb, clb, lits, proof_icb, proof_clb,
+                                                    proof_lits, int(max_vars), int(max_clause_len), out, core, lemma,
+                                                    stream)
+    _capi.check(rc, "satmi_trim_refutations_device")
 
 
 def _proof_of(r, what):

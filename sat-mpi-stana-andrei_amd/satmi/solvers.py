@@ -106,6 +106,19 @@ def check_refutation(formula: Formula, proof) -> bool:
     return check_refutations([formula], [proof])[0]["proven"]
 
 
+def trim_refutation(formula: Formula, proof) -> Optional[Tuple[Formula, List[Clause]]]:
+    """The part of a refutation that matters, found on the GPU by the backward check
+    (refute.trim_refutations): (core_clauses, trimmed_proof) -- the formula's clauses that
+    the refutation uses and the lemmas it needs, in order, the empty clause last -- such that
+    check_refutation(core_clauses, trimmed_proof) holds; None when the trim's status is not
+    PROVEN (no empty lemma, or a needed lemma does not follow)."""
+    from .refute import trim_refutations
+    r = trim_refutations([formula], [proof])[0]
+    if not r["proven"]:
+        return None
+    return [list(formula[c]) for c in r["core"]], r["proof"]
+
+
 def resolution_solver(formula: Formula) -> bool:
     from .resolution import resolution_solve
     return resolution_solve(formula, time_limit=_time_limit)
