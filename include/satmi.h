@@ -562,6 +562,89 @@ int satmi_trim_refutations_host(int num_instances, const int32_t *h_inst_clause_
 /* Test knob of the trim, as satmi_check_debug_grid. */
 int satmi_trim_debug_grid(int workgroups, int waves_per_wg);
 
+/*
+ * Batched witness models: rebuilds an assignment from the record of a
+ * Davis-Putnam elimination or of a resolution saturation that answered True,
+ * and evaluates it against the formula, one wavefront per instance
+ * (csrc/witness.hip).  Instance b has the formula F (m clauses) of the first
+ * CSR triple, the record R (P clauses) of a second triple shaped like the
+ * proofs above, and the stages inst_stage_begin[b] .. inst_stage_begin[b + 1].
+ * Clause index c < m is formula clause c, index m + j record clause j.
+ *   The assignment is total: every variable starts False.  Stage (x, lo, hi),
+ *   0 <= lo <= hi <= m + P, reads the clauses lo .. hi - 1 under the assignment
+ *   as it stands; the stages are processed in order, and ranges may overlap,
+ *   repeat and straddle m.  A clause that holds +x and -x is passed, and with
+ *   highest_only = 1 so is a clause whose largest |literal| is not x.  needP
+ *   holds if some clause holds +x and every other literal of it is false, needN
+ *   likewise with -x; with both the stage is STUCK.  In every case x becomes
+ *   needP (a variable may be decided again by a later stage).  After the last
+ *   stage every clause of F is evaluated: the status is SATMI_WITNESS_MODEL iff
+ *   none is falsified.  The status does not depend on how the stages came
+ *   about, so it is sound for any input; the stuck count is diagnostic.  Every
+ *   output is a function of the inputs alone (not of lane order, grid or clause
+ *   form).
+ *   The record of satmi_dp_host / satmi_dp_batch_host with result 1 gives the
+ *   stages (var[k], the clause list before step k), last step first; that of
+ *   satmi_resolution_host / satmi_resolution_batch_host with result 1 gives one
+ *   stage (v, 0, m + P) per variable, ascending, with highest_only = 1
+ *   (satmi/witness.py builds both).
+ *   max_vars       the table holds a value bit and an "occurs in F" bit for the
+ *                  variables 1 .. max_vars in the wavefront's LDS; at most
+ *                  SATMI_WITNESS_MAX_VARS (satmi_check_models_*'s limit, so any
+ *                  witness can be checked), beyond which the call returns
+ *                  SATMI_ERR_TOO_LARGE before any launch.  A literal 0,
+ *                  INT32_MIN or with |l| > max_vars counts as false (and as a
+ *                  magnitude for highest_only) and sets
+ *                  SATMI_WITNESS_BAD_LITERAL when it is in F or in a clause that
+ *                  a stage reads.  A stage whose variable is outside
+ *                  1 .. max_vars is skipped and sets SATMI_WITNESS_BAD_STAGE.
+ *   max_clause_len longest clause of formulas and records, 0 = unknown: 1 .. 8
+ *                  takes the lane-per-clause form, anything else the
+ *                  wave-per-clause form (same results)
+ *   out            [B x SATMI_WITNESS_NWORDS]: status, stuck stages, index of
+ *                  the first stuck stage relative to the instance's first stage
+ *                  (-1: none), flags, falsified clauses of F, index of the first
+ *                  falsified clause (-1: none)
+ *   row_len, row_lits, stride   [B], [B x stride]: the assignment as a row of
+ *                  satmi_check_models_* (cap = 1): one signed literal per
+ *                  distinct variable that occurs in F with a good literal,
+ *                  ascending by variable, the sign by its final value.  A row
+ *                  longer than stride sets SATMI_WITNESS_ROW_TRUNCATED: its
+ *                  first stride literals are written, row_len holds the count.
+ * The device form is asynchronous on `stream`, owns no device memory, trusts
+ * the CSR ranges and clamps a stage's range to 0 .. m + P.  The host form
+ * checks both triples before any HIP call as satmi_check_refutations_host does
+ * ("formulas: ", "records: "), and refuses ("stages: ") descending
+ * inst_stage_begin, a stage variable outside 1 .. max_vars and a range outside
+ * 0 <= lo <= hi <= m + P; it computes max_vars and max_clause_len itself, writes
+ * 0 to the words of a row behind its length, and is thread-safe: a call leases
+ * a workspace with its own stream.
+ */
+#define SATMI_WITNESS_NWORDS 6          /* per instance: status, stuck, first_stuck (-1), flags, falsified, first_falsified (-1) */
+#define SATMI_WITNESS_NOT_MODEL 0       /* status: the assignment falsifies a clause of F */
+#define SATMI_WITNESS_MODEL 1           /* status: the assignment satisfies every clause of F */
+#define SATMI_WITNESS_BAD_LITERAL 1     /* flags bit: a literal 0, INT32_MIN or |l| > max_vars was read (false) */
+#define SATMI_WITNESS_BAD_STAGE 2       /* flags bit: a stage variable outside 1 .. max_vars (the stage is skipped) */
+#define SATMI_WITNESS_ROW_TRUNCATED 4   /* flags bit: the row is longer than stride */
+#define SATMI_WITNESS_MAX_VARS 524287   /* the largest max_vars: SATMI_CHECK_MAX_VARS */
+int satmi_witness_models_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                const int32_t *d_record_inst_begin, const int32_t *d_record_clause_begin,
+                                const int32_t *d_record_lits, const int32_t *d_inst_stage_begin,
+                                const int32_t *d_stage_var, const int32_t *d_stage_lo, const int32_t *d_stage_hi,
+                                int highest_only, int max_vars, int max_clause_len, int32_t *d_out,
+                                int32_t *d_row_len, int32_t *d_row_lits, int stride, void *stream);
+int satmi_witness_models_host(int num_instances, const int32_t *h_inst_clause_begin,
+                              const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                              const int32_t *h_record_inst_begin, const int32_t *h_record_clause_begin,
+                              const int32_t *h_record_lits, const int32_t *h_inst_stage_begin,
+                              const int32_t *h_stage_var, const int32_t *h_stage_lo, const int32_t *h_stage_hi,
+                              int highest_only, int32_t *h_out, int32_t *h_row_len, int32_t *h_row_lits,
+                              int stride);
+
+/* Test knob of the witness kernel, as satmi_check_debug_grid. */
+int satmi_witness_debug_grid(int workgroups, int waves_per_wg);
+
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into
  * d_span: [0] = ~(first wave's start), [1] = last wave's end, so the launch

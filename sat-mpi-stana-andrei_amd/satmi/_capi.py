@@ -41,6 +41,12 @@ REFUTE_MAX_VARS = 32767
 TRIM_NWORDS = 6
 TRIM_WORDS = ("status", "failed", "first_failed", "flags", "core_clauses", "kept_lemmas")
 TRIM_MAX_VARS = 16383
+# satmi_witness_models_*: words per instance, their names, the statuses, the flags bits, the largest max_vars
+WITNESS_NWORDS = 6
+WITNESS_WORDS = ("status", "stuck", "first_stuck", "flags", "falsified", "first_falsified")
+WITNESS_NOT_MODEL, WITNESS_MODEL = 0, 1
+WITNESS_BAD_LITERAL, WITNESS_BAD_STAGE, WITNESS_ROW_TRUNCATED = 1, 2, 4
+WITNESS_MAX_VARS = 524287
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
 EXPORTED = (
@@ -59,6 +65,7 @@ EXPORTED = (
     "satmi_check_models_device", "satmi_check_models_host", "satmi_check_debug_grid",
     "satmi_check_refutations_device", "satmi_check_refutations_host", "satmi_refute_debug_grid",
     "satmi_trim_refutations_device", "satmi_trim_refutations_host", "satmi_trim_debug_grid",
+    "satmi_witness_models_device", "satmi_witness_models_host", "satmi_witness_debug_grid",
 )
 
 
@@ -197,6 +204,10 @@ def load():
                                                 vp, vp, vp, vp]
     L.satmi_trim_refutations_host.argtypes = [ctypes.c_int, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p]
     L.satmi_trim_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.satmi_witness_models_device.argtypes = [ctypes.c_int] + [vp] * 10 + [ctypes.c_int] * 3 + [vp] * 3 + [
+        ctypes.c_int, vp]
+    L.satmi_witness_models_host.argtypes = [ctypes.c_int] + [i32p] * 10 + [ctypes.c_int] + [i32p] * 3 + [ctypes.c_int]
+    L.satmi_witness_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = library/header mismatch
     _lib = L

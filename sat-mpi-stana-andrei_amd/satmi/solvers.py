@@ -11,6 +11,10 @@ REF.py ("comparatie intre algoritmii de rezolvare a seturilor de clauze.py"):
     hybrid_solver(formula, threshold=1000) -> List[Assignment]                   REF.py:400-404
     pysat_solver(formula) -> List[Assignment]                                    REF.py:387-397
 
+Beside them, what makes an answer checkable: check_assignment (a model),
+check_refutation / trim_refutation (a False of the two saturation solvers) and
+davis_putnam_witness / resolution_witness (a True of theirs, with its model).
+
 The solvers run on the MI355X through libsatmi.so; there is no CPU fallback.
 """
 import random
@@ -141,6 +145,73 @@ def davis_putnam_solver_batch(formulas: List[Formula]) -> List[bool]:
     eliminated one per workgroup; the others go through davis_putnam_solver's path)."""
     from .dp import davis_putnam_solve_batch
     return davis_putnam_solve_batch(formulas, time_limit=_time_limit)
+
+
+def _witnesses(formulas: List[Formula], results, stages_of, highest_only, who):
+    """(answer, model) per formula from the recorded results of one solver: the True answers
+    go through witness.witness_models in one launch."""
+    from .witness import record_of, witness_models
+    true = [b for b, r in enumerate(results) if r["result"] == 1]
+    out: List[Tuple[bool, Optional[Assignment]]] = [(False, None)] * len(results)
+    if true:
+        fs = [formulas[b] for b in true]
+        ws = witness_models(fs, [record_of(results[b]) for b in true],
+                            [stages_of(formulas[b], results[b]) for b in true], highest_only)
+        for b, w in zip(true, ws):
+            if w["status"] != _capi.WITNESS_MODEL:
+                raise _capi.SatmiError(f"{who}: the solver answered True for formula {b}, but the assignment "
+                                       f"rebuilt from its record falsifies {w['falsified']} of its clauses "
+                                       f"(the first: clause {w['first_falsified']}; {w['stuck']} stuck stages)")
+            out[b] = (True, {abs(l): l > 0 for l in w["model"]})
+    return out
+
+
+def davis_putnam_witness_batch(formulas: List[Formula]) -> List[Tuple[bool, Optional[Assignment]]]:
+    """davis_putnam_witness for many formulas: one batched elimination, one witness launch."""
+    from .dp import DavisPutnamLimit, eliminate_batch
+    from .witness import stages_of_elimination
+    formulas = [list(f) for f in formulas]
+    rs = eliminate_batch(formulas, time_limit=_time_limit, record=True)
+    for r in rs:
+        if r["result"] < 0:
+            raise DavisPutnamLimit(f"Davis-Putnam stopped by its limit after {r['steps']} steps")
+    return _witnesses(formulas, rs, stages_of_elimination, False, "davis_putnam_witness")
+
+
+def davis_putnam_witness(formula: Formula) -> Tuple[bool, Optional[Assignment]]:
+    """davis_putnam_solver's answer and, for True, a model {variable: bool} of the formula's
+    variables, rebuilt on the GPU from the elimination's record (satmi/witness.py) and
+    evaluated there against the formula.  Raises SatmiError when the answer is True and the
+    rebuilt assignment is no model: the reference answers True for [[1], []]."""
+    from .dp import DavisPutnamLimit, eliminate
+    from .witness import stages_of_elimination
+    r = eliminate(formula, time_limit=_time_limit, record=True)
+    if r["result"] < 0:
+        raise DavisPutnamLimit(f"Davis-Putnam stopped by its limit after {r['steps']} steps")
+    return _witnesses([formula], [r], stages_of_elimination, False, "davis_putnam_witness")[0]
+
+
+def resolution_witness_batch(formulas: List[Formula]) -> List[Tuple[bool, Optional[Assignment]]]:
+    """resolution_witness for many formulas: one batched saturation, one witness launch."""
+    from .resolution import ResolutionLimit, resolve_batch
+    from .witness import stages_of_resolution
+    formulas = [list(f) for f in formulas]
+    rs = resolve_batch(formulas, time_limit=_time_limit, record=True)
+    for r in rs:
+        if r["result"] < 0:
+            raise ResolutionLimit(f"resolution stopped by its limit after {r['passes']} passes")
+    return _witnesses(formulas, rs, stages_of_resolution, True, "resolution_witness")
+
+
+def resolution_witness(formula: Formula) -> Tuple[bool, Optional[Assignment]]:
+    """resolution_solver's answer and, for True, a model of the formula's variables, rebuilt
+    from the saturation's record as davis_putnam_witness does from the elimination's."""
+    from .resolution import ResolutionLimit, resolve
+    from .witness import stages_of_resolution
+    r = resolve(formula, time_limit=_time_limit, record=True)
+    if r["result"] < 0:
+        raise ResolutionLimit(f"resolution stopped by its limit after {r['passes']} passes")
+    return _witnesses([formula], [r], stages_of_resolution, True, "resolution_witness")[0]
 
 
 def pysat_solver(formula: Formula) -> List[Assignment]:
