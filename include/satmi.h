@@ -413,7 +413,8 @@ int satmi_cdcl_last_stats(double *span_s, double *busy_wave_s, int *resident_wav
  * length outside 0 .. stride is SATMI_ERR_ARG), computes max_vars over the
  * formulas and the rows and max_clause_len itself, and is thread-safe: a call
  * leases a workspace with its own stream, like satmi_resolution_batch_host.
- * UNSAT answers are certified by satmi_check_refutations_* below.
+ * UNSAT answers are certified by satmi_check_refutations_* below (SOUND DPLL's
+ * own through satmi_dpll_refutations_*).
  */
 #define SATMI_CHECK_NWORDS 4          /* per row: falsified, undetermined, first_falsified (-1: none), flags */
 #define SATMI_CHECK_CONTRADICTORY 1   /* flags bit: some v with both +v and -v in the row */
@@ -644,6 +645,84 @@ int satmi_witness_models_host(int num_instances, const int32_t *h_inst_clause_be
 
 /* Test knob of the witness kernel, as satmi_check_debug_grid. */
 int satmi_witness_debug_grid(int workgroups, int waves_per_wg);
+
+/*
+ * Refutations of SATMI_MODE_SOUND DPLL: the batched DPLL above, run by the
+ * general kernel (its LDS form, or SATMI_KERNEL_WIDE for what that form does
+ * not hold; never a clause kernel) in a form that logs why every closed
+ * subtree holds no model, followed by a pack of the logs into the proof triple
+ * of satmi_check_refutations_* / satmi_trim_refutations_* (csrc/dpll.hip,
+ * csrc/dpll_proof.hip).  The search is always SOUND and takes no caller
+ * assignment: an assumption is nothing a lemma could discharge.  Statuses,
+ * counters, models and root assignments are those of satmi_dpll_batch_device;
+ * an instance the general kernel answers SATMI_DPLL_TOO_LARGE stays so.
+ *   A node of the search is its decision path, the frames d1 .. dk (a variable
+ *   and the phase that runs).  The wave logs one lemma whenever a subtree is
+ *   closed without a solution: at a conflict the clause -d1 .. -dk of the path,
+ *   and when a frame is popped after its False phase the same clause of the
+ *   frames below it.  A search that ends SATMI_DPLL_EXHAUSTED with no solution
+ *   logs its tree in post-order and ends with the empty clause, decisions + 1
+ *   lemmas in all, conflicts = decisions / 2 + 1.  Every lemma follows by unit
+ *   propagation from the formula and the lemmas before it: a leaf's because
+ *   what the solver propagated on the path are unit consequences of the
+ *   decisions, an inner node's from its two children's lemmas.  Pure-literal
+ *   assignments are in no lemma and need not be: a literal p is pure when no
+ *   active clause holds -p, so below that point no unit clause and no emptied
+ *   clause counts -p among its false literals; the checker, which never
+ *   assigns p, only has more clauses active, and unit propagation is monotone
+ *   in its premises.
+ *   log, log_begin   instance b logs into log[log_begin[b] .. log_begin[b + 1])
+ *                  (int64 offsets, ascending), one record `len, lit_1 .. lit_len`
+ *                  of signed literals in frame order per lemma.  A record that
+ *                  does not fit is counted and not written.
+ *   info           [B x SATMI_DPLL_PROOF_NWORDS] int64: lemmas logged, log words
+ *                  needed (both exact, whatever the region held), flags
+ *                  (SATMI_DPLL_PROOF_TRUNCATED: the region was too small), and
+ *                  the offset of the instance's first literal in proof_lits
+ *   proof_inst_begin [B + 1], proof_clause_begin [proof_clause_cap + 1],
+ *   proof_lits [proof_lit_cap]   the proof triple.  An instance has its lemmas
+ *                  there when it ended EXHAUSTED with no solution and its log
+ *                  was not truncated, else none (the check reports
+ *                  SATMI_REFUTE_OPEN).
+ *   totals         [2] int64: lemmas and literals of the whole proof.  When they
+ *                  exceed a capacity (or 2^31 - 1), every instance has no lemma,
+ *                  nothing is written past a capacity, and the caller calls
+ *                  again with arrays of the totals' size.
+ * The device form is asynchronous on `stream` and owns no device memory beyond
+ * the per-stream state of satmi_dpll_batch_device; its proof triple feeds the
+ * check and the trim on the same stream with no copy.  The host form checks its
+ * arguments before any HIP call as satmi_dpll_batch_host does (and refuses a
+ * capacity below 1), sizes the log itself and runs again with the counted sizes
+ * until no refuted instance is truncated; h_info and the solution and root
+ * outputs may be NULL.  It is thread-safe: a call leases a workspace with its
+ * own stream.
+ */
+#define SATMI_DPLL_PROOF_NWORDS 4      /* per instance: lemmas, log words needed, flags, first literal offset */
+#define SATMI_DPLL_PROOF_TRUNCATED 1   /* flags bit: the instance's log region was too small */
+int satmi_dpll_refutations_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                  const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                  const int32_t *d_inst_nvars, int max_vars, int max_clauses, int max_lits,
+                                  int max_clause_len, int64_t max_solutions, int64_t node_limit,
+                                  double time_limit_s, int sol_cap, int sol_stride,
+                                  int32_t *d_status, int64_t *d_counters, int32_t *d_sol_len,
+                                  int32_t *d_sol_lits, int32_t *d_root_len, int32_t *d_root_lits,
+                                  int32_t *d_log, const int64_t *d_log_begin,
+                                  int32_t *d_proof_inst_begin, int32_t *d_proof_clause_begin,
+                                  int64_t proof_clause_cap, int32_t *d_proof_lits, int64_t proof_lit_cap,
+                                  int64_t *d_info, int64_t *d_totals, void *stream);
+int satmi_dpll_refutations_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                const int32_t *h_inst_nvars, int64_t max_solutions, int64_t node_limit,
+                                double time_limit_s, int sol_cap, int sol_stride,
+                                int32_t *h_status, int64_t *h_counters, int32_t *h_sol_len,
+                                int32_t *h_sol_lits, int32_t *h_root_len, int32_t *h_root_lits,
+                                int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
+                                int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
+                                int64_t *h_info, int64_t *h_totals);
+
+/* Test knob of satmi_dpll_refutations_host (0 = default): the log words every
+ * instance gets in the first run, so a small search takes the run-again path. */
+int satmi_dpll_refutations_debug_room(int64_t words);
 
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into

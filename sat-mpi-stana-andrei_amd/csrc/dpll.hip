@@ -49,6 +49,7 @@
 
 #include "batch_host.h"
 #include "common.h"
+#include "dpll_proof.h"
 #include "dpll_scan.h"
 
 namespace satmi {
@@ -165,6 +166,15 @@ struct DpllArgs {
     int32_t *root_lits;
     uint32_t *work_counter;
     DpllLayout lay;
+};
+
+// The refutation log of a logging launch (satmi_dpll_refutations_device): instance
+// b writes its lemma records `len, lit_1 .. lit_len` into log[log_begin[b] ..
+// log_begin[b + 1]) and its counts into info[b * SATMI_DPLL_PROOF_NWORDS ..].
+struct ProofLog {
+    int32_t *log;
+    const int64_t *log_begin;
+    int64_t *info;
 };
 
 template <typename T>
@@ -569,9 +579,52 @@ __device__ void unassign_to(const LdsT<T> &S, int ft, int trail_len, int &nsat) 
 
 enum { ST_PROPAGATE = 0, ST_ANALYZE = 1, ST_BACKTRACK = 2, ST_DONE = 3 };
 
+// One lemma of the refutation log: the negated decision literals of the frames
+// fvar[0, nframes), in frame order (True ran first: a frame in its False phase
+// decided -v).  Lanes write the frames in parallel; a record that does not fit
+// the region's `room` words is counted and not written.
 template <typename T>
-__device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b) {
+__device__ __forceinline__ void log_lemma(const LdsT<T> &S, int32_t *rec, int64_t room, int nframes, int64_t &lemmas,
+                                          int64_t &words) {
+    const int64_t need = 1 + (int64_t)nframes;
+    if (words + need <= room) {
+        int32_t *r = rec + words;
+        if (lane_id() == 0) r[0] = nframes;
+        for (int i = lane_id(); i < nframes; i += 64) {
+            const uint32_t fv = S.fvar[i];
+            const int v = (int)(fv & ~T::PHASE);
+            r[1 + i] = (fv & T::PHASE) ? v : -v;
+        }
+    }
+    ++lemmas;
+    words += need;
+}
+
+// The counts of instance b's log: lemmas, words needed, truncated.
+__device__ __forceinline__ void log_close(const ProofLog &PL, int b, int64_t lemmas, int64_t words, int64_t room) {
+    if (lane_id() == 0) {
+        int64_t *w = PL.info + (int64_t)b * SATMI_DPLL_PROOF_NWORDS;
+        w[0] = lemmas;
+        w[1] = words;
+        w[2] = words > room ? SATMI_DPLL_PROOF_TRUNCATED : 0;
+        w[3] = 0;
+    }
+}
+
+// LOG: the search writes its refutation (SOUND mode, no caller assignment): one
+// lemma for every subtree closed without a solution, the clause of the negated
+// decisions on the path to it -- at a conflict, and when a frame is popped
+// after its False phase.
+template <typename T, bool LOG = false>
+__device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b, const ProofLog *PL = nullptr) {
     const uint64_t t_start = __builtin_amdgcn_s_memrealtime();
+    int64_t lemmas = 0, lwords = 0, lroom = 0;
+    int32_t *lrec = nullptr;
+    if constexpr (LOG) {
+        const int64_t at = PL->log_begin[b];
+        lrec = PL->log + at;
+        lroom = PL->log_begin[b + 1] - at;
+    }
     PhaseClock ph;
     ph.start();
     const int ln = lane_id();
@@ -593,6 +646,7 @@ __device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b) {
             A.status[b] = SATMI_DPLL_TOO_LARGE;
             if (A.root_len) A.root_len[b] = 0;
         }
+        if constexpr (LOG) log_close(*PL, b, 0, 0, lroom);
         return;
     }
     // ---- stage the instance into LDS
@@ -625,6 +679,7 @@ __device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b) {
             A.status[b] = SATMI_DPLL_TOO_LARGE;
             if (A.root_len) A.root_len[b] = 0;
         }
+        if constexpr (LOG) log_close(*PL, b, 0, 0, lroom);
         return;
     }
     for (int i = ln; i < L; i += 64) {
@@ -743,6 +798,7 @@ __device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b) {
             }
             if (conflict) {
                 ++conflicts;
+                if constexpr (LOG) log_lemma(S, lrec, lroom, depth, lemmas, lwords);
                 state = ST_BACKTRACK;
             } else {
                 state = ST_ANALYZE;
@@ -836,6 +892,7 @@ __device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b) {
                     break;
                 }
                 --depth;
+                if constexpr (LOG) log_lemma(S, lrec, lroom, depth, lemmas, lwords);
             }
             PH_MARK(PH_BACKTRACK);
         }
@@ -860,6 +917,7 @@ __device__ void solve_instance(const DpllArgs &A, const LdsT<T> &S, int b) {
         ctr[SATMI_CTR_ROUNDS] = rounds;
         ctr[SATMI_CTR_TICKS] = (int64_t)(__builtin_amdgcn_s_memrealtime() - t_start);
     }
+    if constexpr (LOG) log_close(*PL, b, lemmas, lwords, lroom);
 #ifdef SATMI_PHASE_STAMPS
     PH_MARK(PH_OTHER);
     if (A.root_lits && A.sol_stride >= 16 && ln < 8)
@@ -891,15 +949,15 @@ __device__ __forceinline__ LdsT<T> bind_storage(unsigned char *base, const DpllL
 
 // Persistent grid: every wave pulls instance indices from a global counter until
 // the batch is drained (instances differ wildly in search-tree size).
-template <typename T>
-__device__ __forceinline__ void run_batch(const DpllArgs &A, const LdsT<T> &S) {
+template <typename T, bool LOG = false>
+__device__ __forceinline__ void run_batch(const DpllArgs &A, const LdsT<T> &S, const ProofLog *PL = nullptr) {
     span_begin(A.work_counter);
     for (;;) {
         uint32_t b = 0;
         if (lane_id() == 0) b = atomicAdd(A.work_counter, 1u);
         b = uniform_u32(b);
         if (b >= (uint32_t)A.num_instances) break;
-        solve_instance<T>(A, S, (int)b);
+        solve_instance<T, LOG>(A, S, (int)b, PL);
         wave_sync();
     }
     span_end(A.work_counter);
@@ -919,6 +977,20 @@ __global__ void __launch_bounds__(64) dpll_wide_kernel(DpllArgs A, unsigned char
     LdsT<Wide> S = bind_storage<Wide>(arena + (size_t)blockIdx.x * (size_t)A.lay.bytes, A.lay);
     S.mark = mark_s;
     run_batch<Wide>(A, S);
+}
+
+// The logging forms of the two kernels above (satmi_dpll_refutations_device).
+__global__ void __launch_bounds__(256) dpll_log_batch_kernel(DpllArgs A, ProofLog PL) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int wave = threadIdx.x >> 6;
+    run_batch<Narrow, true>(A, bind_storage<Narrow>(smem + (size_t)wave * A.lay.bytes, A.lay), &PL);
+}
+
+__global__ void __launch_bounds__(64) dpll_log_wide_kernel(DpllArgs A, unsigned char *arena, ProofLog PL) {
+    __shared__ __attribute__((aligned(16))) int32_t mark_s[64];
+    LdsT<Wide> S = bind_storage<Wide>(arena + (size_t)blockIdx.x * (size_t)A.lay.bytes, A.lay);
+    S.mark = mark_s;
+    run_batch<Wide, true>(A, S, &PL);
 }
 
 // ------------------------------------------------------------------ host side
@@ -981,10 +1053,11 @@ struct KernelChoice {
     bool scan() const { return kind == SATMI_KERNEL_SCAN || kind == SATMI_KERNEL_INC; }
 };
 static KernelChoice choose_kernel(int policy, int mode, bool has_init, int max_vars, int max_clauses, int max_lits,
-                                  int max_clause_len) {
+                                  int max_clause_len, bool clause_kernels = true) {
     KernelChoice ch;
     ch.inc = policy != SATMI_KERNEL_SCAN;
-    if (mode == SATMI_MODE_SOUND && !has_init && policy != SATMI_KERNEL_GENERAL &&
+    // (a logging launch has no clause kernel to take: clause_kernels = false)
+    if (clause_kernels && mode == SATMI_MODE_SOUND && !has_init && policy != SATMI_KERNEL_GENERAL &&
         dpll_scan_eligible(max_vars, max_clauses, max_lits, max_clause_len, ch.inc, &ch.scan_lds)) {
         ch.kind = ch.inc ? SATMI_KERNEL_INC : SATMI_KERNEL_SCAN;
         return ch;
@@ -1009,6 +1082,7 @@ static std::atomic<int> g_kernel_policy{SATMI_KERNEL_AUTO};
 static std::atomic<int> g_split_enable{1};
 static std::atomic<int> g_split_helpers{SPLIT_HELPERS_PER_CU};
 static std::atomic<int> g_split_warmup{SPLIT_WARMUP_NODES};
+static std::atomic<int64_t> g_proof_debug_room{0};   // satmi_dpll_refutations_debug_room
 
 // The state of `stream` on the current device: made with its work counter when
 // the stream has none and `create` is set, else *out = nullptr.
@@ -1048,6 +1122,54 @@ static NarrowShape narrow_shape(uint32_t lds_bytes_per_wave) {
     }
     return S;
 }
+
+// The general kernel's launch on st's stream, in its wide or its LDS form; with
+// `log`, the logging form of either.
+static int general_launch(const DpllArgs &A, bool wide, const DeviceFacts &dev, DpllStream *st, const ProofLog *log) {
+    hipStream_t s = st->stream;
+    const DpllLayout &lay = A.lay;
+    const int num_instances = A.num_instances;
+    if (wide) {
+        // one-wave workgroups, each with an HBM arena; resident waves bounded by
+        // 32 per CU and by half the free device memory
+        size_t free_b = 0, total_b = 0;
+        SATMI_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t per = lay.bytes;
+        const size_t by_mem = std::max<size_t>(1, (free_b / 2) / per);
+        const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)dev.cus * 32, by_mem});
+        if (st->scratch(st->arena, (size_t)grid * per) != SATMI_OK) {
+            set_error("wide DPLL arenas: hipMalloc failed");
+            return SATMI_ERR_NOMEM;
+        }
+        if (log)
+            hipLaunchKernelGGL(dpll_log_wide_kernel, dim3(grid), dim3(64), 0, s, A, st->arena.as<unsigned char>(),
+                               *log);
+        else
+            hipLaunchKernelGGL(dpll_wide_kernel, dim3(grid), dim3(64), 0, s, A, st->arena.as<unsigned char>());
+        SATMI_HIP(hipGetLastError());
+        return SATMI_OK;
+    }
+    // Occupancy is set by LDS (narrow_shape: the shape satmi_dpll_plan reports)
+    const NarrowShape shape = narrow_shape(lay.bytes);
+    const uint32_t wg_lds = lay.bytes * (uint32_t)shape.waves_per_wg;
+    const int need = (num_instances + shape.waves_per_wg - 1) / shape.waves_per_wg;
+    const int grid = std::max(1, std::min(need, dev.cus * shape.wg_per_cu));
+    if (wg_lds > 64u * 1024u)
+        SATMI_HIP(hipFuncSetAttribute(log ? (const void *)dpll_log_batch_kernel : (const void *)dpll_batch_kernel,
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds));
+    if (log)
+        hipLaunchKernelGGL(dpll_log_batch_kernel, dim3(grid), dim3(64 * shape.waves_per_wg), wg_lds, s, A, *log);
+    else
+        hipLaunchKernelGGL(dpll_batch_kernel, dim3(grid), dim3(64 * shape.waves_per_wg), wg_lds, s, A);
+    SATMI_HIP(hipGetLastError());
+    return SATMI_OK;
+}
+
+// The workspace a satmi_dpll_refutations_host call leases: one carved block for
+// the batch, the proof and the outputs, and the log.
+struct DpllProofWork : WorkStream {
+    DevBuf block, log;
+};
 
 // A host copy of the splitting scratch head of the stream's last DPLL launch;
 // *split = false (and no copy) when that launch did not split.
@@ -1272,34 +1394,74 @@ extern "C" int satmi_dpll_batch_device(int num_instances, const int32_t *d_inst_
     A.mode = mode;
     A.work_counter = st->counter;
     A.lay = lay;
-    const bool wide = ch.kind == SATMI_KERNEL_WIDE;
-    if (wide) {
-        // one-wave workgroups, each with an HBM arena; resident waves bounded by
-        // 32 per CU and by half the free device memory
-        size_t free_b = 0, total_b = 0;
-        SATMI_HIP(hipMemGetInfo(&free_b, &total_b));
-        const size_t per = lay.bytes;
-        const size_t by_mem = std::max<size_t>(1, (free_b / 2) / per);
-        const int grid = (int)std::min<size_t>({(size_t)num_instances, (size_t)dev.cus * 32, by_mem});
-        if (st->scratch(st->arena, (size_t)grid * per) != SATMI_OK) {
-            set_error("wide DPLL arenas: hipMalloc failed");
-            return SATMI_ERR_NOMEM;
-        }
-        hipLaunchKernelGGL(dpll_wide_kernel, dim3(grid), dim3(64), 0, s, A, st->arena.as<unsigned char>());
-        SATMI_HIP(hipGetLastError());
-        return SATMI_OK;
+    return general_launch(A, ch.kind == SATMI_KERNEL_WIDE, dev, st, nullptr);
+}
+
+extern "C" int satmi_dpll_refutations_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                             const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                             const int32_t *d_inst_nvars, int max_vars, int max_clauses,
+                                             int max_lits, int max_clause_len, int64_t max_solutions,
+                                             int64_t node_limit, double time_limit_s, int sol_cap, int sol_stride,
+                                             int32_t *d_status, int64_t *d_counters, int32_t *d_sol_len,
+                                             int32_t *d_sol_lits, int32_t *d_root_len, int32_t *d_root_lits,
+                                             int32_t *d_log, const int64_t *d_log_begin,
+                                             int32_t *d_proof_inst_begin, int32_t *d_proof_clause_begin,
+                                             int64_t proof_clause_cap, int32_t *d_proof_lits,
+                                             int64_t proof_lit_cap, int64_t *d_info, int64_t *d_totals,
+                                             void *stream) {
+    const char *who = "satmi_dpll_refutations_device";
+    if (num_instances < 0) return fail_arg(who, "negative formula count");
+    if (proof_clause_cap < 1 || proof_lit_cap < 1) return fail_arg(who, "non-positive proof capacity");
+    if (sol_cap < 0 || (sol_cap > 0 && (!d_sol_len || !d_sol_lits || sol_stride < max_vars)))
+        return fail_arg(who, "solution buffers too small (sol_stride < max_vars)");
+    if (d_root_lits && sol_stride < max_vars) return fail_arg(who, "root buffer stride < max_vars");
+    if (num_instances == 0) return SATMI_OK;
+    if (!d_inst_clause_begin || !d_clause_lit_begin || !d_inst_nvars || !d_status || !d_counters || !d_log ||
+        !d_log_begin || !d_proof_inst_begin || !d_proof_clause_begin || !d_proof_lits || !d_info || !d_totals)
+        return fail_arg(who, "null pointer");
+    // the general kernel in the form satmi_dpll_batch_device would give it, were there no clause kernels
+    int policy = g_kernel_policy.load();
+    if (policy == SATMI_KERNEL_SCAN || policy == SATMI_KERNEL_INC) policy = SATMI_KERNEL_AUTO;
+    const KernelChoice ch = choose_kernel(policy, SATMI_MODE_SOUND, false, max_vars, max_clauses, max_lits,
+                                          max_clause_len, false);
+    if (ch.rc) {
+        set_error(std::string(who) + ": instance too large (wide layout: vars < 2^30, clauses <= 2^28, literals <= "
+                                     "2^30, < 4 GiB per wave)");
+        return ch.rc;
     }
-    // Occupancy is set by LDS (narrow_shape: the shape satmi_dpll_plan reports)
-    const NarrowShape shape = narrow_shape(lay.bytes);
-    const uint32_t wg_lds = lay.bytes * (uint32_t)shape.waves_per_wg;
-    const int need = (num_instances + shape.waves_per_wg - 1) / shape.waves_per_wg;
-    const int grid = std::max(1, std::min(need, dev.cus * shape.wg_per_cu));
-    if (wg_lds > 64u * 1024u)
-        SATMI_HIP(hipFuncSetAttribute((const void *)dpll_batch_kernel,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)wg_lds));
-    hipLaunchKernelGGL(dpll_batch_kernel, dim3(grid), dim3(64 * shape.waves_per_wg), wg_lds, s, A);
-    SATMI_HIP(hipGetLastError());
-    return SATMI_OK;
+    hipStream_t s = (hipStream_t)stream;
+    DpllStream *st = nullptr;
+    SATMI_TRY(dpll_stream(s, true, &st));
+    DeviceFacts dev;
+    SATMI_TRY(device_facts(&dev));
+    const uint64_t time_limit_ticks = time_limit_s > 0 ? (uint64_t)(time_limit_s * dev.ticks_per_s) : 0;
+    const DpllBatch batch{d_inst_clause_begin, d_clause_lit_begin, d_lits, d_inst_nvars,   // (DpllBatch's order)
+                          num_instances, sol_cap, sol_stride,
+                          max_solutions, node_limit, time_limit_ticks,
+                          d_status, d_counters, d_sol_len, d_sol_lits, d_root_len, d_root_lits};
+    st->split_last = false;
+    SATMI_HIP(hipMemsetAsync(st->counter, 0, 24, s));   // counter + launch span (common.h)
+    DpllArgs A{};
+    bind_batch(A, batch);
+    A.mode = SATMI_MODE_SOUND;
+    A.work_counter = st->counter;
+    A.lay = ch.lay;
+    const ProofLog PL{d_log, d_log_begin, d_info};
+    SATMI_TRY(general_launch(A, ch.kind == SATMI_KERNEL_WIDE, dev, st, &PL));
+    ProofPack P{};
+    P.num_instances = num_instances;
+    P.status = d_status;
+    P.counters = d_counters;
+    P.log = d_log;
+    P.log_begin = d_log_begin;
+    P.info = d_info;
+    P.pib = d_proof_inst_begin;
+    P.pcb = d_proof_clause_begin;
+    P.plits = d_proof_lits;
+    P.clause_cap = proof_clause_cap;
+    P.lit_cap = proof_lit_cap;
+    P.totals = d_totals;
+    return dpll_proof_pack(P, s);
 }
 
 extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
@@ -1386,4 +1548,149 @@ extern "C" int satmi_dpll_batch_host(int num_instances, const int32_t *h_inst_cl
     SATMI_TRY(d.down(h_root_lits, o_rlits, 4 * B * (size_t)sol_stride));
     const hipError_t e = hipStreamSynchronize(d.stream);
     return e == hipSuccess ? SATMI_OK : hip_fail(e, "hipStreamSynchronize");
+}
+
+extern "C" int satmi_dpll_refutations_debug_room(int64_t words) {
+    if (words < 0) return fail_arg("satmi_dpll_refutations_debug_room", "words >= 0");
+    g_proof_debug_room.store(words);
+    return SATMI_OK;
+}
+
+extern "C" int satmi_dpll_refutations_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                           const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                           const int32_t *h_inst_nvars, int64_t max_solutions, int64_t node_limit,
+                                           double time_limit_s, int sol_cap, int sol_stride, int32_t *h_status,
+                                           int64_t *h_counters, int32_t *h_sol_len, int32_t *h_sol_lits,
+                                           int32_t *h_root_len, int32_t *h_root_lits, int32_t *h_proof_inst_begin,
+                                           int32_t *h_proof_clause_begin, int64_t proof_clause_cap,
+                                           int32_t *h_proof_lits, int64_t proof_lit_cap, int64_t *h_info,
+                                           int64_t *h_totals) {
+    const char *who = "satmi_dpll_refutations_host";
+    // ---- check: all of it before any HIP call
+    CsrShape sh;
+    std::vector<int32_t> nv((size_t)std::max(num_instances, 0));
+    const char *own = proof_clause_cap < 1 || proof_lit_cap < 1 ? "non-positive proof capacity"
+                      : sol_cap < 0                             ? "negative sol_cap"
+                                                                : nullptr;
+    const bool outs = h_inst_nvars && h_status && h_counters && h_proof_inst_begin && h_proof_clause_begin &&
+                      h_proof_lits && h_totals;
+    if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits, own, outs,
+                                          &sh, nv.data()))
+        return fail_arg(who, bad);
+    if (num_instances == 0) return SATMI_OK;
+    const int C = sh.C, Ltot = (int)sh.Ltot;
+    int max_vars = 0;
+    for (int b = 0; b < num_instances; ++b) {
+        if (h_inst_nvars[b] < 0) return fail_arg(who, "negative inst_nvars");
+        if (nv[(size_t)b] > h_inst_nvars[b]) return fail_arg(who, "literal beyond inst_nvars");
+        max_vars = std::max(max_vars, h_inst_nvars[b]);
+    }
+    if (sol_stride < max_vars) return fail_arg(who, "sol_stride < number of variables");
+    if (proof_clause_cap > INT32_MAX - 1 || proof_lit_cap > INT32_MAX)
+        return fail_arg(who, "proof capacity beyond the 32-bit offsets of the proof arrays");
+
+    // ---- lease the workspace
+    int dev = 0;
+    DeviceFacts facts;
+    SATMI_TRY(device_facts(&facts, &dev));
+    Lease<DpllProofWork> lease{Pool<DpllProofWork>::get().acquire(dev)};
+    if (!lease.w) {
+        set_error(std::string(who) + ": hipStreamCreate failed");
+        return SATMI_ERR_HIP;
+    }
+    DpllProofWork &wk = *lease.w;
+    hipStream_t s = wk.stream;
+    // ---- carve one block: the batch, the solve's outputs, the log ranges, the proof
+    const size_t B = (size_t)num_instances;
+    const size_t cap1 = (size_t)std::max(sol_cap, 1), stride1 = (size_t)std::max(sol_stride, 1);
+    Carve cv;
+    const size_t o_icb = cv.take(4 * (B + 1));
+    const size_t o_clb = cv.take(4 * (size_t)(C + 1));
+    const size_t o_lits = cv.take(4 * (size_t)std::max(Ltot, 1));
+    const size_t o_nv = cv.take(4 * B);
+    const size_t o_st = cv.take(4 * B);
+    const size_t o_ctr = cv.take(8 * B * SATMI_NCOUNTERS);
+    const size_t o_sl = cv.take(4 * B * cap1);
+    const size_t o_sol = cv.take(4 * B * cap1 * stride1);
+    const size_t o_rl = cv.take(4 * B);
+    const size_t o_rlits = cv.take(4 * B * stride1);
+    const size_t o_lb = cv.take(8 * (B + 1));
+    const size_t o_info = cv.take(8 * B * SATMI_DPLL_PROOF_NWORDS);
+    const size_t o_tot = cv.take(16);
+    const size_t o_pib = cv.take(4 * (B + 1));
+    const size_t o_pcb = cv.take(4 * ((size_t)proof_clause_cap + 1));
+    const size_t o_plits = cv.take(4 * (size_t)proof_lit_cap);
+    static constexpr OomText OOM{"satmi_dpll_refutations_host", "split the batch"};
+    SATMI_TRY(wk.block.reserve(cv.at, &OOM));
+    const Staged d{wk.block.as<unsigned char>(), s};
+    SATMI_TRY(d.up(o_icb, h_inst_clause_begin, 4 * (B + 1)));
+    SATMI_TRY(d.up(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)));
+    SATMI_TRY(d.up(o_lits, h_lits, 4 * (size_t)Ltot));
+    SATMI_TRY(d.up(o_nv, h_inst_nvars, 4 * B));
+    // the same rule as satmi_dpll_batch_host's: the true maximum above 5 or with no empty clause
+    const int max_clause_len = (C > 0 && (sh.min_len >= 1 || sh.max_len > 5)) ? sh.max_len : 0;
+
+    // ---- solve and pack; again with the counted sizes while a refuted instance's log was truncated
+    // (the search is deterministic, so the second run fits; time limits may take more)
+    const int64_t dbg_room = g_proof_debug_room.load();
+    std::vector<int64_t> room(B, dbg_room > 0 ? dbg_room
+                                              : std::min<int64_t>(65536, std::max<int64_t>(256, ((int64_t)16 << 20) /
+                                                                                                    (int64_t)B)));
+    std::vector<int64_t> lb(B + 1), info(B * SATMI_DPLL_PROOF_NWORDS);
+    std::vector<int32_t> status(B);
+    std::vector<int64_t> counters(B * SATMI_NCOUNTERS);
+    for (int round = 0;; ++round) {
+        lb[0] = 0;
+        for (size_t b = 0; b < B; ++b) lb[b + 1] = lb[b] + room[b];
+        SATMI_TRY(wk.log.reserve(4 * (size_t)lb[B], &OOM));
+        SATMI_TRY(d.up(o_lb, lb.data(), 8 * (B + 1)));
+        SATMI_TRY(satmi_dpll_refutations_device(
+            num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
+            d.at<const int32_t>(o_nv), max_vars, sh.max_clauses, sh.max_lits, max_clause_len, max_solutions,
+            node_limit, time_limit_s, sol_cap, sol_stride, d.at<int32_t>(o_st), d.at<int64_t>(o_ctr),
+            d.at<int32_t>(o_sl), d.at<int32_t>(o_sol), d.at<int32_t>(o_rl), d.at<int32_t>(o_rlits),
+            wk.log.as<int32_t>(), d.at<const int64_t>(o_lb), d.at<int32_t>(o_pib), d.at<int32_t>(o_pcb),
+            proof_clause_cap, d.at<int32_t>(o_plits), proof_lit_cap, d.at<int64_t>(o_info), d.at<int64_t>(o_tot),
+            s));
+        SATMI_TRY(d.down(info.data(), o_info, 8 * B * SATMI_DPLL_PROOF_NWORDS));
+        SATMI_TRY(d.down(status.data(), o_st, 4 * B));
+        SATMI_TRY(d.down(counters.data(), o_ctr, 8 * B * SATMI_NCOUNTERS));
+        SATMI_HIP(hipStreamSynchronize(s));
+        bool again = false;
+        for (size_t b = 0; b < B; ++b) {
+            const int64_t *w = &info[b * SATMI_DPLL_PROOF_NWORDS];
+            if ((w[2] & SATMI_DPLL_PROOF_TRUNCATED) && status[b] == SATMI_DPLL_EXHAUSTED &&
+                counters[b * SATMI_NCOUNTERS + SATMI_CTR_SOLUTIONS] == 0) {
+                room[b] = std::max(room[b], w[1]);
+                again = true;
+            }
+        }
+        if (!again) break;
+        if (round == 7) {
+            set_error(std::string(who) + ": the logs still outgrow their counted sizes after 8 runs");
+            return SATMI_ERR_TOO_LARGE;
+        }
+    }
+    lease.ok = true;   // the stream is drained; the next call trusts nothing of the workspace
+    // ---- copy back
+    int64_t totals[2] = {0, 0};
+    SATMI_TRY(d.down(totals, o_tot, 16));
+    SATMI_TRY(d.down(h_proof_inst_begin, o_pib, 4 * (B + 1)));
+    SATMI_TRY(d.down(h_sol_len, o_sl, sol_cap > 0 ? 4 * B * (size_t)sol_cap : 0));
+    SATMI_TRY(d.down(h_sol_lits, o_sol, sol_cap > 0 ? 4 * B * (size_t)sol_cap * (size_t)sol_stride : 0));
+    SATMI_TRY(d.down(h_root_len, o_rl, 4 * B));
+    SATMI_TRY(d.down(h_root_lits, o_rlits, 4 * B * (size_t)sol_stride));
+    SATMI_HIP(hipStreamSynchronize(s));
+    const bool fits = totals[0] <= proof_clause_cap && totals[1] <= proof_lit_cap;
+    // (totals that do not fit: no instance has a lemma, and proof_clause_begin is its first word)
+    SATMI_TRY(d.down(h_proof_clause_begin, o_pcb, 4 * (size_t)((fits ? totals[0] : 0) + 1)));
+    SATMI_TRY(d.down(h_proof_lits, o_plits, fits ? 4 * (size_t)totals[1] : 0));
+    SATMI_HIP(hipStreamSynchronize(s));
+    std::memcpy(h_status, status.data(), 4 * B);
+    std::memcpy(h_counters, counters.data(), 8 * B * SATMI_NCOUNTERS);
+    if (h_info) std::memcpy(h_info, info.data(), 8 * B * SATMI_DPLL_PROOF_NWORDS);
+    h_totals[0] = totals[0];
+    h_totals[1] = totals[1];
+    if (wk.log.cap > ((size_t)256 << 20)) wk.log.release();   // a large log is not kept in the pool
+    return SATMI_OK;
 }

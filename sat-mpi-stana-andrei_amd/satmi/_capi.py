@@ -47,6 +47,10 @@ WITNESS_WORDS = ("status", "stuck", "first_stuck", "flags", "falsified", "first_
 WITNESS_NOT_MODEL, WITNESS_MODEL = 0, 1
 WITNESS_BAD_LITERAL, WITNESS_BAD_STAGE, WITNESS_ROW_TRUNCATED = 1, 2, 4
 WITNESS_MAX_VARS = 524287
+# satmi_dpll_refutations_*: int64 words per instance, their names, the flags bit
+DPLL_PROOF_NWORDS = 4
+DPLL_PROOF_WORDS = ("lemmas", "log_words", "flags", "first_literal")
+DPLL_PROOF_TRUNCATED = 1
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
 EXPORTED = (
@@ -66,6 +70,7 @@ EXPORTED = (
     "satmi_check_refutations_device", "satmi_check_refutations_host", "satmi_refute_debug_grid",
     "satmi_trim_refutations_device", "satmi_trim_refutations_host", "satmi_trim_debug_grid",
     "satmi_witness_models_device", "satmi_witness_models_host", "satmi_witness_debug_grid",
+    "satmi_dpll_refutations_device", "satmi_dpll_refutations_host", "satmi_dpll_refutations_debug_room",
 )
 
 
@@ -208,6 +213,14 @@ def load():
         ctypes.c_int, vp]
     L.satmi_witness_models_host.argtypes = [ctypes.c_int] + [i32p] * 10 + [ctypes.c_int] + [i32p] * 3 + [ctypes.c_int]
     L.satmi_witness_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.satmi_dpll_refutations_device.argtypes = (
+        [ctypes.c_int] + [vp] * 4 + [ctypes.c_int] * 4 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_double,
+                                                        ctypes.c_int, ctypes.c_int]
+        + [vp] * 6 + [vp, vp] + [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp])
+    L.satmi_dpll_refutations_host.argtypes = (
+        [ctypes.c_int] + [i32p] * 4 + [ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int, ctypes.c_int]
+        + [i32p, i64p, i32p, i32p, i32p, i32p] + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64, i64p, i64p])
+    L.satmi_dpll_refutations_debug_room.argtypes = [ctypes.c_int64]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = library/header mismatch
     _lib = L

@@ -21,6 +21,8 @@ trim_refutations (csrc/trim.hip) is the backward form: from the first empty lemm
 downwards it checks only the lemmas that lemma needs, and returns which formula
 clauses (the UNSAT core) and which lemmas (the trimmed proof) the refutation uses.
 """
+import ctypes
+
 import numpy as np
 
 from . import _capi
@@ -159,3 +161,102 @@ def proof_of_elimination(r):
     clause list after every completed step, in order, and the empty clause exactly
     when the result is 0."""
     return _proof_of(r, "proof_of_elimination")
+
+
+# ---- refutations of sound DPLL's UNSAT answers (csrc/dpll.hip's logging kernels, csrc/dpll_proof.hip)
+def _logging_args(mode, inits, who):
+    """A lemma cannot discharge an assumption and REF-mode decisions do not rewrite the
+    formula: logging is SOUND mode without a caller assignment (satmi.h: SATMI_ERR_ARG)."""
+    if mode != "sound" or inits is not None:
+        raise _capi.SatmiError(f"{who} failed ({_capi.ERR_ARG}): {who}: logging needs SOUND mode and no caller "
+                               "assignment")
+
+
+def dpll_refutations_packed(batch, max_solutions=1, node_limit=0, time_limit=0.0, sol_cap=None, mode="sound",
+                            inits=None, room=None):
+    """satmi_dpll_refutations_host on a CnfBatch: sound DPLL by the logging general kernel.
+    Returns (DpllResult, proof CnfBatch, int64 [B, 4] info: _capi.DPLL_PROOF_WORDS).  Formula
+    b's lemmas are "formula" b of the proof batch: the refutation of an instance that ended
+    exhausted with no solution, else no lemma.  `room` = (lemmas, literals) the first call's
+    proof arrays hold; a proof that outgrows them is asked for again with 4x the room (the
+    totals, if those are more)."""
+    from .dpll import DpllResult
+    _logging_args(mode, inits, "satmi_dpll_refutations_host")
+    L = _capi.load()
+    _capi.require_gpu()
+    B = batch.num_instances
+    if sol_cap is None:
+        sol_cap = max(1, max_solutions) if max_solutions > 0 else 1024
+    stride = max(1, int(batch.inst_nvars.max(initial=0)))
+    status = np.zeros(B, dtype=np.int32)
+    counters = np.zeros((B, _capi.NCOUNTERS), dtype=np.int64)
+    sol_len = np.zeros((B, max(sol_cap, 1)), dtype=np.int32)
+    sol_lits = np.zeros((B, max(sol_cap, 1), stride), dtype=np.int32)
+    root_len = np.zeros(B, dtype=np.int32)
+    root_lits = np.zeros((B, stride), dtype=np.int32)
+    info = np.zeros((B, _capi.DPLL_PROOF_NWORDS), dtype=np.int64)
+    totals = np.zeros(2, dtype=np.int64)
+    pib = np.zeros(B + 1, dtype=np.int32)
+    ccap, lcap = room if room is not None else (max(1024, 64 * B), max(16384, 1024 * B))
+    i64 = ctypes.c_int64
+    while True:
+        pcb = np.zeros(ccap + 1, dtype=np.int32)
+        plits = np.zeros(lcap, dtype=np.int32)
+        rc = L.satmi_dpll_refutations_host(
+            B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits), _p(batch.inst_nvars),
+            int(max_solutions), int(node_limit), float(time_limit), int(sol_cap), int(stride), _p(status),
+            _p(counters, i64), _p(sol_len), _p(sol_lits), _p(root_len), _p(root_lits), _p(pib), _p(pcb), int(ccap),
+            _p(plits), int(lcap), _p(info, i64), _p(totals, i64))
+        _capi.check(rc, "satmi_dpll_refutations_host")
+        if B == 0 or (int(totals[0]) <= ccap and int(totals[1]) <= lcap):
+            break
+        # truncated: again with 4x the room
+        ccap, lcap = max(4 * ccap, int(totals[0])), max(4 * lcap, int(totals[1]))
+    P = int(pib[B]) if B else 0
+    proof = CnfBatch(pib, pcb[:P + 1].copy(), plits[:max(int(pcb[P]), 1)].copy(),   # (as pack: never an empty array)
+                     np.zeros(B, dtype=np.int32))   # (inst_nvars of a proof batch: unused by the checks)
+    return DpllResult(status, counters, sol_len, sol_lits, root_len, root_lits), proof, info
+
+
+def dpll_refutations(formulas, max_solutions=1, node_limit=0, time_limit=0.0, mode="sound", inits=None, room=None):
+    """Sound DPLL on `formulas` (a CnfBatch or a list of formulas) with its refutations.  One
+    dict per formula: "status" (_capi.DPLL_*), "counters" (name -> count), "sat" (True: a
+    model was found; False: exhausted without one; None: a limit stopped the search),
+    "model" (signed literals in assignment order, or None), "root" (the assignment after
+    the root's unit propagation), "proof" (the lemma clauses that refute the formula, the
+    empty clause last: what check_refutations verifies; None unless sat is False) and
+    "lemmas" / "log_words" (what the search logged)."""
+    batch = formulas if isinstance(formulas, CnfBatch) else pack(formulas)
+    r, proof, info = dpll_refutations_packed(batch, max_solutions, node_limit, time_limit, None, mode, inits, room)
+    out = []
+    for b in range(batch.num_instances):
+        nsol = r.num_solutions(b)
+        st = int(r.status[b])
+        sat = True if nsol > 0 else False if st == _capi.DPLL_EXHAUSTED else None
+        out.append({"status": st, "counters": r.counter_dict(b), "sat": sat,
+                    "model": r.solutions(b)[0] if nsol > 0 else None, "root": r.root_assignment(b),
+                    "proof": [list(c) for c in proof.instance(b)] if sat is False else None,
+                    "lemmas": int(info[b, 0]), "log_words": int(info[b, 1])})
+    return out
+
+
+def proof_of_dpll(r):
+    """The proof in a dpll_refutations dict: the logged lemmas of an UNSAT answer."""
+    if r.get("sat") is not False or r.get("proof") is None:
+        raise ValueError("proof_of_dpll: the search did not end exhausted without a model: it has no refutation")
+    return [list(c) for c in r["proof"]]
+
+
+def dpll_refutations_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clauses, max_lits,
+                            max_clause_len, status, counters, sol_len, sol_lits, root_len, root_lits, sol_cap,
+                            sol_stride, log, log_begin, proof_icb, proof_clb, proof_clause_cap, proof_lits,
+                            proof_lit_cap, info, totals, max_solutions=1, node_limit=0, time_limit=0.0, stream=None):
+    """satmi_dpll_refutations_device on device pointers (ints, e.g. a tensor's data_ptr());
+    asynchronous on `stream`.  The proof triple it writes is what check_refutations_device
+    and trim_refutations_device read, on the same stream with no copy."""
+    rc = _capi.load().satmi_dpll_refutations_device(
+        int(num_instances), icb, clb, lits, inst_nvars, int(max_vars), int(max_clauses), int(max_lits),
+        int(max_clause_len), int(max_solutions), int(node_limit), float(time_limit), int(sol_cap), int(sol_stride),
+        status, counters, sol_len, sol_lits, root_len, root_lits, log, log_begin, proof_icb, proof_clb,
+        int(proof_clause_cap), proof_lits, int(proof_lit_cap), info, totals, stream)
+    _capi.check(rc, "satmi_dpll_refutations_device")

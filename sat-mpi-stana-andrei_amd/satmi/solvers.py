@@ -12,7 +12,8 @@ REF.py ("comparatie intre algoritmii de rezolvare a seturilor de clauze.py"):
     pysat_solver(formula) -> List[Assignment]                                    REF.py:387-397
 
 Beside them, what makes an answer checkable: check_assignment (a model),
-check_refutation / trim_refutation (a False of the two saturation solvers) and
+check_refutation / trim_refutation (a False of the two saturation solvers, or
+the proof dpll_refutation returns with sound DPLL's UNSAT) and
 davis_putnam_witness / resolution_witness (a True of theirs, with its model).
 
 The solvers run on the MI355X through libsatmi.so; there is no CPU fallback.
@@ -91,6 +92,27 @@ def dpll_solve(formula: Formula):
     if r.num_solutions(0) > 0:
         return True, {abs(l): l > 0 for l in r.solutions(0)[0]}
     return False, None
+
+
+def dpll_refutation_batch(formulas: List[Formula]):
+    """dpll_refutation for many formulas in one launch."""
+    from .refute import dpll_refutations
+    out = []
+    for r in dpll_refutations([list(f) for f in formulas], max_solutions=1, time_limit=_time_limit):
+        st = r["status"]
+        if st == _capi.DPLL_TIMEOUT:
+            raise SolverTimeout(f"Timeout after {_time_limit:g} seconds")
+        if st not in (_capi.DPLL_EXHAUSTED, _capi.DPLL_STOPPED):   # nothing was decided: never an UNSAT verdict
+            raise _capi.SatmiError(f"dpll_refutation: GPU search ended with status {_capi.STATUS_NAMES.get(st, st)}")
+        out.append((True, {abs(l): l > 0 for l in r["model"]}) if r["sat"] else (False, r["proof"]))
+    return out
+
+
+def dpll_refutation(formula: Formula):
+    """dpll_solve with a certificate either way: (True, model), or (False, proof) where
+    `proof` is the search's refutation -- one lemma per closed subtree, the clause of its
+    negated decisions, the empty clause last -- and check_refutation(formula, proof) holds."""
+    return dpll_refutation_batch([formula])[0]
 
 
 def check_assignment(formula: Formula, assignment) -> bool:
