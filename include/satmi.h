@@ -724,6 +724,150 @@ int satmi_dpll_refutations_host(int num_instances, const int32_t *h_inst_clause_
  * instance gets in the first run, so a small search takes the run-again path. */
 int satmi_dpll_refutations_debug_room(int64_t words);
 
+/*
+ * Sound CDCL: a clause-learning search whose learned clauses are its proof, one
+ * wavefront per formula, batched over a persistent grid (csrc/cdcl_sound.hip).
+ * Unlike satmi_cdcl_batch_host above, which mirrors the reference's CDCLSolver
+ * step for step, this is a decision procedure: it answers SAT with a model that
+ * is a row of satmi_check_models_*, or UNSAT with a refutation that
+ * satmi_check_refutations_* / satmi_trim_refutations_* read.  Every output is a
+ * function of the formula and conflict_limit alone (not of the grid, of lane
+ * timing or of the clause form), by the rule below; tests/cdcl_sound_rows.py
+ * restates it in Python.
+ *   Clause indices: formula clauses are 0 .. m-1, learned clause j is m + j.
+ *   Evaluating a clause: a repeated literal counts once; a clause is satisfied
+ *   if some literal is true, falsified if every literal is false (the empty
+ *   clause always is), unit if no literal is true and all its unassigned
+ *   literals are one and the same literal.  A clause that holds +v and -v is
+ *   therefore never unit or falsified.
+ *   Propagation runs in rounds.  Every clause is evaluated under the assignment
+ *   as it stood at the round's start.  If any clause is falsified, the conflict
+ *   is the lowest-indexed one and the round implies nothing.  Otherwise each
+ *   variable implied by some unit clause takes the sign and the reason of the
+ *   lowest-indexed clause implying it, at the current decision level, and the
+ *   implied variables enter the trail in ascending order of that clause index.
+ *   A round that implies nothing is the fixpoint.
+ *   Conflicts: a conflict at level 0 gives UNSAT.  Otherwise, if conflict_limit
+ *   > 0 and this is conflict number conflict_limit, the instance ends LIMIT.
+ *   Otherwise first-UIP analysis runs backwards over the trail: starting from
+ *   the conflict clause, the literals of the clause at hand (but the one just
+ *   resolved on) whose variables are above level 0 are marked; the clause at
+ *   hand becomes the reason of the marked variable nearest the trail's end,
+ *   which loses its mark, until that variable is the only marked one of the
+ *   current level.  Level-0 literals are dropped.  The learned clause is the
+ *   negation of that variable's trail literal (the asserting literal), first,
+ *   and the negated trail literals of the other marked variables in descending
+ *   trail position.  The search backjumps to the highest level among the
+ *   others, or to 0 for a unit clause: every variable above that level is
+ *   unassigned and its value saved as its phase.  Each variable of the learned
+ *   clause gains 1 activity; after a conflict whose number is a multiple of 256
+ *   every activity is halved (integers, rounding down).  Propagation follows;
+ *   its first round finds the learned clause unit.
+ *   Decisions, at a fixpoint: the candidates are the unassigned variables that
+ *   occur in the formula.  SAT holds when none is left.  Otherwise the one of
+ *   the highest activity, the lowest id on a tie, opens a new level with its
+ *   saved phase, initially False.  There are no restarts.
+ *   max_vars       the wavefront's LDS holds, per variable of 0 .. max_vars, a
+ *                  32-bit reason, a mark bit, 16 bits each of level, trail and
+ *                  activity, and a byte of value, phase and "occurs": 89 KiB at
+ *                  SATMI_CDCL_SOUND_MAX_VARS, beyond which the call returns
+ *                  SATMI_ERR_TOO_LARGE before any launch.  An instance with
+ *                  inst_nvars[b] > max_vars, or a literal 0, INT32_MIN or beyond
+ *                  inst_nvars[b], ends SATMI_CDCL_SOUND_TOO_LARGE untouched.
+ *   max_clause_len longest clause of the formulas, 0 = unknown: 1 .. 8 takes the
+ *                  lane-per-clause form, anything else the wave-per-clause form
+ *                  (same results); learned clauses are always read wave-per-clause
+ *   time_limit_s   per-instance wall-clock limit (<= 0 = none), looked at once per
+ *                  conflict and decision: the instance ends LIMIT
+ *   lemmas, lemma_begin   instance b keeps its learned clauses in
+ *                  lemmas[lemma_begin[b] .. lemma_begin[b + 1]) (int64 offsets,
+ *                  ascending), one record `len, lit_1 .. lit_len` each, in the order
+ *                  learned: the clause database and the proof log at once.  On
+ *                  UNSAT the record `0`, the empty clause, closes it.  A record
+ *                  that does not fit is counted and never written, in part or
+ *                  whole, and the instance ends FULL (so does one whose offsets
+ *                  m + words would pass 2^31 - 1).
+ *   status         [B] SATMI_CDCL_SOUND_*
+ *   counters       [B x SATMI_CDCL_SOUND_NCOUNTERS] int64: conflicts, decisions,
+ *                  propagated literals, rounds, learned clauses, learned
+ *                  literals, highest level, restarts (0)
+ *   row_len, row_lits, stride   [B], [B x stride]: for SAT the model as a row of
+ *                  satmi_check_models_* (cap = 1): one signed literal per variable
+ *                  that occurs in the formula, ascending; row_len holds the count,
+ *                  the first stride literals are written.  Else row_len is 0.
+ *   info           [B x SATMI_CDCL_SOUND_NWORDS] int64: records (the closing
+ *                  empty clause and a record that did not fit included), region
+ *                  words needed, flags (SATMI_CDCL_SOUND_TRUNCATED with FULL), and,
+ *                  after the pack, the offset of the instance's first literal
+ *                  in proof_lits
+ * The device form is asynchronous on `stream` and owns no device memory.  The
+ * pack, on the same stream, turns the regions into the proof triple (as
+ * satmi_dpll_refutations_device's does: an instance has its lemmas there when
+ * it ended UNSAT, else none; totals [2] = lemmas and literals of the whole
+ * proof, and when they exceed a capacity every instance has no lemma and
+ * nothing is written past a capacity), so the solve, the pack, the check and the
+ * trim run on one stream with no copy.
+ * Why the proof checks: when clause j is learned, assigning its literals false
+ * repeats, for the checker, the trail below the asserting level together with
+ * the negated UIP; every reason clause the analysis resolved on then becomes
+ * unit in reverse resolution order (its other literals are false: they are in
+ * the learned clause, or were resolved on later, or hold at level 0, which unit
+ * propagation over F and the earlier lemmas reaches as the solver did), and the
+ * conflict clause is falsified.  The checker's propagation is a fixpoint, so
+ * order does not matter.  The closing empty clause follows from the level-0
+ * conflict in the same way.
+ * The host form checks its arguments before any HIP call as
+ * satmi_dpll_refutations_host does (and refuses stride < the largest inst_nvars),
+ * sizes the regions itself and runs again with four times the room while an
+ * instance ended FULL, up to room_cap words per instance (0 = as much as the
+ * 32-bit offsets allow).  A run-again repeats the whole batch, the instances
+ * that had finished included (only the FULL ones get more room; the search is
+ * deterministic, so the others end as before): one outlier costs its batch up
+ * to a dozen runs, and a caller who expects one gives it a batch of its own or
+ * a room_cap.  Likewise a proof that outgrows proof_clause_cap / proof_lit_cap
+ * is reported in h_totals with no lemma written, and the call that fetches it
+ * with larger arrays solves again.  h_info alone of the outputs may be NULL (an
+ * output the caller does not want); a proof capacity beyond the 32-bit offsets
+ * of the proof arrays (2^31 - 2 lemmas, 2^31 - 1 literals) is refused.  It is
+ * thread-safe: a call leases a workspace with its own stream.
+ */
+#define SATMI_CDCL_SOUND_UNSAT 0
+#define SATMI_CDCL_SOUND_SAT 1
+#define SATMI_CDCL_SOUND_LIMIT 2       /* conflict_limit or time_limit_s stopped it */
+#define SATMI_CDCL_SOUND_FULL 3        /* a learned clause did not fit the instance's region */
+#define SATMI_CDCL_SOUND_TOO_LARGE 4   /* the instance does not fit the launch's layout */
+#define SATMI_CDCL_SOUND_NCOUNTERS 8
+#define SATMI_CDCL_SOUND_NWORDS 4      /* per instance: records, region words needed, flags, first literal offset */
+#define SATMI_CDCL_SOUND_TRUNCATED 1   /* flags bit: the instance's region was too small */
+#define SATMI_CDCL_SOUND_MAX_VARS 8191 /* the largest max_vars: an 89 KiB region in a CU's 160 KiB */
+int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                  const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                  const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                  int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                  const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                  int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                  void *stream);
+int satmi_cdcl_sound_pack_device(int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
+                                 const int64_t *d_lemma_begin, int64_t *d_info, int32_t *d_proof_inst_begin,
+                                 int32_t *d_proof_clause_begin, int64_t proof_clause_cap, int32_t *d_proof_lits,
+                                 int64_t proof_lit_cap, int64_t *d_totals, void *stream);
+int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                int64_t room_cap, int32_t *h_status, int64_t *h_counters, int32_t *h_row_len,
+                                int32_t *h_row_lits, int stride, int32_t *h_proof_inst_begin,
+                                int32_t *h_proof_clause_begin, int64_t proof_clause_cap, int32_t *h_proof_lits,
+                                int64_t proof_lit_cap, int64_t *h_info, int64_t *h_totals);
+
+/* Test knobs of the sound CDCL (0 = default): the grid as satmi_check_debug_grid;
+ * the region words every instance gets in the host form's first run, so a small
+ * search takes the run-again path. */
+int satmi_cdcl_sound_debug_grid(int workgroups, int waves_per_wg);
+int satmi_cdcl_sound_debug_room(int64_t words);
+
+/* LDS bytes one wavefront needs at this max_vars (0 = beyond the limit). */
+uint64_t satmi_cdcl_sound_lds_bytes(int max_vars);
+
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into
  * d_span: [0] = ~(first wave's start), [1] = last wave's end, so the launch

@@ -1,0 +1,115 @@
+"""Sound CDCL on the GPU (libsatmi.so, csrc/cdcl_sound.hip): a clause-learning search,
+one wavefront per formula, whose learned clauses are its refutation.
+
+Unlike satmi.cdcl, the reference's CDCLSolver step for step, this is a decision
+procedure.  A SAT answer carries a model that check.check_models accepts; an UNSAT
+answer carries the learned clauses in learning order, closed by the empty clause,
+which refute.check_refutations and refute.trim_refutations verify.  Every output is
+a function of the formula alone: include/satmi.h states the search rule in full and
+tests/cdcl_sound_rows.py restates it in Python.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _capi
+from ._batch import _p
+from .cnf import CnfBatch, pack
+
+
+def debug_grid(workgroups=0, waves_per_wg=0):
+    """Test knob (0 = default): at most `workgroups` workgroups of `waves_per_wg` (1, 2, 4) wavefronts."""
+    _capi.check(_capi.load().satmi_cdcl_sound_debug_grid(int(workgroups), int(waves_per_wg)),
+                "satmi_cdcl_sound_debug_grid")
+
+
+def debug_room(words=0):
+    """Test knob (0 = default): the region words every formula gets in the host form's first run."""
+    _capi.check(_capi.load().satmi_cdcl_sound_debug_room(int(words)), "satmi_cdcl_sound_debug_room")
+
+
+def lds_bytes(max_vars):
+    """LDS bytes one wavefront needs at this max_vars (0 = beyond CDCL_SOUND_MAX_VARS)."""
+    return int(_capi.load().satmi_cdcl_sound_lds_bytes(int(max_vars)))
+
+
+def cdcl_sound_packed(batch, conflict_limit=0, time_limit=0.0, room_cap=0, room=None):
+    """satmi_cdcl_sound_batch_host on a CnfBatch.  Returns (status int32 [B], counters int64
+    [B, 8]: _capi.CDCL_SOUND_COUNTERS, row_len int32 [B], row_lits int32 [B, stride], proof
+    CnfBatch, info int64 [B, 4]: _capi.CDCL_SOUND_WORDS).  Formula b's lemmas are "formula" b of
+    the proof batch: the refutation of an UNSAT instance, else no lemma.  `room_cap` = the most
+    region words a formula may take (0 = no cap of the caller's): one that needs more ends
+    CDCL_SOUND_FULL.  `room` = (lemmas, literals) the first call's proof arrays hold; a proof that
+    outgrows them is asked for again with 4x the room (the totals, if those are more)."""
+    L = _capi.load()
+    _capi.require_gpu()
+    B = batch.num_instances
+    stride = max(1, int(batch.inst_nvars.max(initial=0)))
+    status = np.zeros(B, dtype=np.int32)
+    counters = np.zeros((B, _capi.CDCL_SOUND_NCOUNTERS), dtype=np.int64)
+    row_len = np.zeros(B, dtype=np.int32)
+    row_lits = np.zeros((B, stride), dtype=np.int32)
+    info = np.zeros((B, _capi.CDCL_SOUND_NWORDS), dtype=np.int64)
+    totals = np.zeros(2, dtype=np.int64)
+    pib = np.zeros(B + 1, dtype=np.int32)
+    ccap, lcap = room if room is not None else (max(1024, 64 * B), max(16384, 1024 * B))
+    i64 = ctypes.c_int64
+    while True:
+        pcb = np.zeros(ccap + 1, dtype=np.int32)
+        plits = np.zeros(lcap, dtype=np.int32)
+        rc = L.satmi_cdcl_sound_batch_host(
+            B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits), _p(batch.inst_nvars),
+            int(conflict_limit), float(time_limit), int(room_cap), _p(status), _p(counters, i64), _p(row_len),
+            _p(row_lits), int(stride), _p(pib), _p(pcb), int(ccap), _p(plits), int(lcap), _p(info, i64),
+            _p(totals, i64))
+        _capi.check(rc, "satmi_cdcl_sound_batch_host")
+        if B == 0 or (int(totals[0]) <= ccap and int(totals[1]) <= lcap):
+            break
+        ccap, lcap = max(4 * ccap, int(totals[0])), max(4 * lcap, int(totals[1]))
+    P = int(pib[B]) if B else 0
+    proof = CnfBatch(pib, pcb[:P + 1].copy(), plits[:max(int(pcb[P]), 1)].copy(),   # (as pack: never an empty array)
+                     np.zeros(B, dtype=np.int32))   # (inst_nvars of a proof batch: unused by the checks)
+    return status, counters, row_len, row_lits, proof, info
+
+
+def cdcl_sound_batch(formulas, conflict_limit=0, time_limit=0.0, room_cap=0, room=None):
+    """Sound CDCL on `formulas` (a CnfBatch or a list of formulas).  One dict per formula:
+    "status" (_capi.CDCL_SOUND_*), "sat" (True / False / None: a limit, a full region or the
+    layout stopped the search), "counters" (name -> count), "model" (one signed literal per
+    variable of the formula, ascending, or None), "proof" (the learned clauses in learning
+    order, the empty clause last: what check_refutations verifies; None unless sat is False)
+    and "records" / "region_words" (what the search needed of its region)."""
+    batch = formulas if isinstance(formulas, CnfBatch) else pack(formulas)
+    status, counters, row_len, row_lits, proof, info = cdcl_sound_packed(batch, conflict_limit, time_limit,
+                                                                        room_cap, room)
+    out = []
+    for b in range(batch.num_instances):
+        st = int(status[b])
+        sat = True if st == _capi.CDCL_SOUND_SAT else False if st == _capi.CDCL_SOUND_UNSAT else None
+        out.append({"status": st, "sat": sat,
+                    "counters": dict(zip(_capi.CDCL_SOUND_COUNTERS, map(int, counters[b]))),
+                    "model": row_lits[b, :int(row_len[b])].tolist() if sat else None,
+                    "proof": [list(c) for c in proof.instance(b)] if sat is False else None,
+                    "records": int(info[b, 0]), "region_words": int(info[b, 1])})
+    return out
+
+
+def cdcl_sound_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clause_len, lemmas, lemma_begin,
+                      status, counters, row_len, row_lits, stride, info, conflict_limit=0, time_limit=0.0,
+                      stream=None):
+    """satmi_cdcl_sound_batch_device on device pointers (ints, e.g. a tensor's data_ptr());
+    asynchronous on `stream`."""
+    rc = _capi.load().satmi_cdcl_sound_batch_device(
+        int(num_instances), icb, clb, lits, inst_nvars, int(max_vars), int(max_clause_len), int(conflict_limit),
+        float(time_limit), lemmas, lemma_begin, status, counters, row_len, row_lits, int(stride), info, stream)
+    _capi.check(rc, "satmi_cdcl_sound_batch_device")
+
+
+def pack_device(num_instances, status, lemmas, lemma_begin, info, proof_icb, proof_clb, proof_clause_cap,
+                proof_lits, proof_lit_cap, totals, stream=None):
+    """satmi_cdcl_sound_pack_device: the regions of a cdcl_sound_device solve as the proof triple
+    that check_refutations_device and trim_refutations_device read, on the same stream."""
+    rc = _capi.load().satmi_cdcl_sound_pack_device(
+        int(num_instances), status, lemmas, lemma_begin, info, proof_icb, proof_clb, int(proof_clause_cap),
+        proof_lits, int(proof_lit_cap), totals, stream)
+    _capi.check(rc, "satmi_cdcl_sound_pack_device")

@@ -247,6 +247,14 @@ def proof_of_dpll(r):
     return [list(c) for c in r["proof"]]
 
 
+def proof_of_cdcl(r):
+    """The proof in a cdcl_sound.cdcl_sound_batch dict: the learned clauses of an UNSAT answer,
+    in learning order, the empty clause last."""
+    if r.get("sat") is not False or r.get("proof") is None:
+        raise ValueError("proof_of_cdcl: the search did not end UNSAT: it has no refutation")
+    return [list(c) for c in r["proof"]]
+
+
 def dpll_refutations_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clauses, max_lits,
                             max_clause_len, status, counters, sol_len, sol_lits, root_len, root_lits, sol_cap,
                             sol_stride, log, log_begin, proof_icb, proof_clb, proof_clause_cap, proof_lits,

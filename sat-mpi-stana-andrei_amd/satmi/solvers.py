@@ -14,7 +14,9 @@ REF.py ("comparatie intre algoritmii de rezolvare a seturilor de clauze.py"):
 Beside them, what makes an answer checkable: check_assignment (a model),
 check_refutation / trim_refutation (a False of the two saturation solvers, or
 the proof dpll_refutation returns with sound DPLL's UNSAT) and
-davis_putnam_witness / resolution_witness (a True of theirs, with its model).
+davis_putnam_witness / resolution_witness (a True of theirs, with its model);
+cdcl_sound_solve, the library's own clause-learning search, returns a model or a
+proof of that kind, and answers for pysat_solver where PySAT is not installed.
 
 The solvers run on the MI355X through libsatmi.so; there is no CPU fallback.
 """
@@ -236,14 +238,41 @@ def resolution_witness(formula: Formula) -> Tuple[bool, Optional[Assignment]]:
     return _witnesses([formula], [r], stages_of_resolution, True, "resolution_witness")[0]
 
 
+def cdcl_sound_solve(formula: Formula):
+    """The library's own clause-learning decision procedure (csrc/cdcl_sound.hip):
+    (True, model, None) with model {variable: bool} over the formula's variables, or
+    (False, None, proof) where `proof` is the learned clauses in learning order, the empty
+    clause last, and check_refutation(formula, proof) holds.  Raises SolverTimeout under the
+    driver's deadline and SatmiError when the formula is beyond the kernel's layout or its
+    learned clauses outgrow their region."""
+    from .cdcl_sound import cdcl_sound_batch
+    from .refute import proof_of_cdcl
+    r = cdcl_sound_batch([list(formula)], time_limit=_time_limit)[0]
+    st = r["status"]
+    if st == _capi.CDCL_SOUND_LIMIT:
+        raise SolverTimeout(f"Timeout after {_time_limit:g} seconds")
+    if r["sat"] is None:   # nothing was decided: never an UNSAT verdict
+        raise _capi.SatmiError("cdcl_sound_solve: GPU search ended with status "
+                               f"{_capi.CDCL_SOUND_STATUS_NAMES.get(st, st)}")
+    if r["sat"]:
+        return True, {abs(l): l > 0 for l in r["model"]}, None
+    return False, None, proof_of_cdcl(r)
+
+
 def pysat_solver(formula: Formula) -> List[Assignment]:
-    """REF.py:387-397 delegates to PySAT's Glucose3, a third-party library that
-    is not part of this image.  It is used when installed; otherwise this raises."""
+    """REF.py:387-397 delegates to PySAT's Glucose3, a third-party clause-learning solver.
+    It is used when installed; otherwise the library's own sound CDCL answers
+    (cdcl_sound_solve), in PySAT's model shape: one dict over the variables
+    1 .. max |literal|, those that do not occur False, or [] for UNSAT."""
     try:
         from pysat.formula import CNF
         from pysat.solvers import Solver
-    except ImportError as e:  # pragma: no cover - depends on the environment
-        raise ImportError("pysat_solver needs the python-sat package (REF.py:6-7)") from e
+    except ImportError:
+        sat, model, _ = cdcl_sound_solve(formula)
+        if not sat:
+            return []
+        top = max((abs(l) for c in formula for l in c), default=0)
+        return [{v: model.get(v, False) for v in range(1, top + 1)}]
     cnf = CNF()
     for clause in formula:
         cnf.append(clause)
