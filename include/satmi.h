@@ -868,6 +868,98 @@ int satmi_cdcl_sound_debug_room(int64_t words);
 /* LDS bytes one wavefront needs at this max_vars (0 = beyond the limit). */
 uint64_t satmi_cdcl_sound_lds_bytes(int max_vars);
 
+/*
+ * Sound CDCL under assumptions: is F satisfiable under the literals a_1 .. a_k,
+ * and if not, which of them are to blame?  The assumption-carrying form of the
+ * search above (csrc/cdcl_sound.hip, its own kernel instantiations; the ones
+ * above keep their machine code).  Instance b assumes
+ * assume_lits[assume_begin[b] .. assume_begin[b + 1]) (int32 offsets, ascending),
+ * in that order.  Every output is a function of the formula, the assumption
+ * list and conflict_limit alone, by the rule above with these additions;
+ * tests/cdcl_assume_rows.py restates it in Python.
+ *   Occurs: a variable occurs if it is in the formula or in the assumptions.
+ *   Decision candidates and the model row are over these variables, so
+ *   inst_nvars[b] covers the assumptions' variables too.
+ *   Assumption levels: level i <= k belongs to a_i.  At a fixpoint with the
+ *   current level cur < k, let a = a_(cur+1).  If a is true, cur becomes cur + 1:
+ *   an empty level; nothing is assigned and nothing is counted as a decision.  If
+ *   a is unassigned, cur becomes cur + 1 and a is assigned at that level with no
+ *   reason, as a decision is, and enters the trail; it is not counted in
+ *   `decisions`.  In both cases the highest level is updated and propagation
+ *   follows with its own round.  If a is false, the instance ends
+ *   SATMI_CDCL_SOUND_ASSUMED, UNSAT under the assumptions, after the final
+ *   analysis below.  Free decisions start only once cur >= k; SAT is answered
+ *   only there.  Conflicts, analysis, learning, backjumps, activities, phases
+ *   and conflict_limit are unchanged: a backjump below level k simply re-opens
+ *   the assumption levels in order, and a conflict at level 0 is UNSAT as
+ *   before, with an empty core and a refutation of F alone.
+ *   Final analysis, when a is false: the core starts as [a], and var(a) is
+ *   marked if its level is above 0.  The trail is walked from its end down to
+ *   the first level-0 entry: a marked variable with no reason (at these levels
+ *   always an assumption) appends its trail literal to the core; a marked
+ *   variable with a reason marks the other literals of its reason clause whose
+ *   level is above 0.  The core is therefore a first, then assumptions in
+ *   descending trail position: a sublist of the assumptions as literals, [a]
+ *   alone when -a holds at level 0, [a, -a] when the assumptions contradict
+ *   each other.  It need not be minimal.
+ *   Limits: an instance with more than SATMI_CDCL_SOUND_MAX_VARS assumptions, or
+ *   with an assumption literal 0, INT32_MIN or beyond inst_nvars[b], ends
+ *   TOO_LARGE untouched; levels therefore stay below 2^16.  The assumptions are
+ *   read from the caller's arrays where they lie, never copied to LDS.
+ *   core_len, core_lits, core_stride   [B], [B x core_stride]: for ASSUMED the
+ *                  core; core_len holds the count, the first core_stride
+ *                  literals are written (core_stride >= 0; a core has at most
+ *                  k literals).  Else core_len is 0.
+ * With ASSUMED the region is closed by the empty record, as with UNSAT (and ends
+ * FULL, with no core, when that record does not fit).  satmi_cdcl_assume_pack_device
+ * is the pack above that also gives ASSUMED instances their lemmas; the pack
+ * above is unchanged and gives them none.
+ * Why the proof checks: the lemma list, the empty clause last, is a RUP
+ * refutation of F together with the core's literals as unit clauses.  Every
+ * lemma but the last is RUP from F and the earlier lemmas alone, by the argument
+ * above: an assumption is on the trail as a decision is, and the analysis never
+ * resolves on it, so no lemma depends on the assumptions but through its own
+ * literals.  The empty clause follows because unit propagation over F, the
+ * lemmas and the core's units reaches -a as the solver's assumption levels did:
+ * the final analysis marked exactly the variables that the derivation of -a
+ * rests on above level 0, each of them either a core literal, which is a unit
+ * clause, or implied by a reason clause whose other literals are marked or hold
+ * at level 0, which propagation reaches as the solver did; and a itself is a
+ * unit clause, so -a falsifies it.  The checker's propagation is a fixpoint, so
+ * order does not matter.  satmi_check_refutations_* and satmi_trim_refutations_*
+ * read that pair as they read any other; neither kernel changes.
+ * With no assumptions (assume_begin all equal) every output -- status, counters,
+ * model row, region words, info -- equals satmi_cdcl_sound_batch_*'s.
+ * The host form checks its arguments before any HIP call as
+ * satmi_cdcl_sound_batch_host does, and the assumption arrays as
+ * satmi_dpll_batch_host checks its init ranges (NULL or descending
+ * assume_begin, an assumption literal 0, INT32_MIN or beyond inst_nvars[b] and a
+ * negative core_stride are refused; h_core_lits may be NULL when core_stride is
+ * 0); it shares the run-again loop, the workspace pool and the thread safety.
+ */
+#define SATMI_CDCL_SOUND_ASSUMED 5     /* UNSAT under the assumptions: core_len / core_lits hold the failed ones */
+int satmi_cdcl_assume_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                   const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                   const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                   int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                   const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                   int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                   const int32_t *d_assume_begin, const int32_t *d_assume_lits, int32_t *d_core_len,
+                                   int32_t *d_core_lits, int core_stride, void *stream);
+int satmi_cdcl_assume_pack_device(int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
+                                  const int64_t *d_lemma_begin, int64_t *d_info, int32_t *d_proof_inst_begin,
+                                  int32_t *d_proof_clause_begin, int64_t proof_clause_cap, int32_t *d_proof_lits,
+                                  int64_t proof_lit_cap, int64_t *d_totals, void *stream);
+int satmi_cdcl_assume_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                 const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                 const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                 int64_t room_cap, int32_t *h_status, int64_t *h_counters, int32_t *h_row_len,
+                                 int32_t *h_row_lits, int stride, int32_t *h_proof_inst_begin,
+                                 int32_t *h_proof_clause_begin, int64_t proof_clause_cap, int32_t *h_proof_lits,
+                                 int64_t proof_lit_cap, int64_t *h_info, int64_t *h_totals,
+                                 const int32_t *h_assume_begin, const int32_t *h_assume_lits, int32_t *h_core_len,
+                                 int32_t *h_core_lits, int core_stride);
+
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into
  * d_span: [0] = ~(first wave's start), [1] = last wave's end, so the launch

@@ -33,6 +33,12 @@
 //     wave-per-clause), the learned records wave-per-clause along their chain.
 //   * Every loop carries its bound in its condition; a record that does not fit
 //     the region is counted and never written, in part or whole.
+//   * Under assumptions (satmi_cdcl_assume_batch_device, restated in
+//     tests/cdcl_assume_rows.py) level i <= k belongs to assumption i, read from
+//     the caller's array at each fixpoint below level k; a false one ends the
+//     search with the final analysis, a walk down the trail along the reasons
+//     that collects the failed assumptions.  The search kernel and the pack's
+//     scan are compiled twice from cdcl_sound_search.inc, without and with it.
 //
 // Plain C++ and vector memory operations only.  The translation unit shares no
 // device code with any other kernel, whose machine code stays what it is.
@@ -77,6 +83,14 @@ struct CsArgs {
     uint32_t max_vars, region_words;
     int64_t conflict_limit;
     uint64_t time_limit_ticks;
+};
+
+// The same under assumptions: instance b assumes assume_lits[assume_begin[b] ..
+// assume_begin[b + 1]), in that order, and answers with its failed ones.
+struct CsAssumeArgs : CsArgs {
+    const int32_t *assume_begin, *assume_lits;
+    int32_t *core_len, *core_lits;             // [B], [B x core_stride]
+    int core_stride;
 };
 
 struct CsWave {
@@ -217,297 +231,6 @@ __device__ __forceinline__ const int32_t *cs_clause(const CsWave &w, int code, i
     return p + 1;
 }
 
-template <bool LONG>
-__global__ void __launch_bounds__(256) cdcl_sound_kernel(CsArgs A) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t cs_lds[];
-    const int ln = lane_id(), wv = (int)threadIdx.x >> 6, wpg = (int)blockDim.x >> 6;
-    const uint64_t lt = lanemask_lt();
-    CsWave w;
-    {
-        uint32_t *base = cs_lds + (size_t)wv * A.region_words;
-        w.reason = (int32_t *)base;
-        w.seen = base + cs_reason_words(A.max_vars);
-        w.level = (uint16_t *)(w.seen + cs_seen_words(A.max_vars));
-        w.trail = w.level + 2u * cs_half_words(A.max_vars);
-        w.act = w.trail + 2u * cs_half_words(A.max_vars);
-        w.flags = (uint8_t *)(w.act + 2u * cs_half_words(A.max_vars));
-    }
-    w.lits = A.lits;
-    const int64_t W = (int64_t)gridDim.x * wpg;
-    for (int64_t b = (int64_t)blockIdx.x * wpg + wv; b < A.num_instances; b += W) {
-        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-        const int c0 = A.icb[b];
-        w.m = A.icb[b + 1] - c0;
-        w.fclb = A.clb + c0;
-        w.nv = A.nvars[b];
-        const int64_t lb = A.lemma_begin[b];
-        w.rec = A.lemmas + lb;
-        w.room = max((int64_t)0, A.lemma_begin[b + 1] - lb);
-        w.used = 0;
-        w.trail_len = w.ncand = w.cur = 0;
-        int status = CS_RUNNING;
-        int64_t conflicts = 0, decisions = 0, props = 0, rounds = 0, learned = 0, learned_lits = 0, top = 0;
-        int64_t records = 0, words = 0;   // what the search needed of its region, exact
-        int row = 0;
-        const int ls = w.fclb[0], le = w.fclb[w.m];
-        // ---- the instance must fit the layout: no LDS index beyond the region
-        {
-            bool bad = false;
-            for (int j = ls + ln; j < le; j += 64) bad |= cs_var(A.lits[j]) - 1u >= (uint32_t)max(w.nv, 0);
-            if (w.nv < 0 || (uint32_t)w.nv > A.max_vars || __ballot(bad) != 0ull) status = SATMI_CDCL_SOUND_TOO_LARGE;
-        }
-        if (status == CS_RUNNING) {
-            for (int v = ln; v <= w.nv; v += 64) {
-                w.reason[v] = CS_NONE;
-                w.level[v] = 0;
-                w.act[v] = 0;
-                w.flags[v] = 0;
-            }
-            for (int t = ln; t < (int)cs_seen_words((uint32_t)w.nv); t += 64) w.seen[t] = 0u;
-            wave_sync();
-            for (int j = ls + ln; j < le; j += 64) w.flags[cs_var(A.lits[j])] = 8u;   // occurs (every lane the same byte value)
-            wave_sync();
-        }
-        // Every pass of the loop ends the instance, learns a clause (two words of
-        // the region at least) or decides (at most nv decisions between conflicts).
-        const uint64_t pass_cap = ((uint64_t)w.room / 2u + 2u) * ((uint64_t)max(w.nv, 0) + 2u);
-        for (uint64_t pass = 0; status == CS_RUNNING && pass < pass_cap; ++pass) {
-            // ---- unit propagation in rounds, to a conflict or the fixpoint
-            int confl = -1;
-            for (int r = 0; r <= w.nv && confl < 0; ++r) {
-                ++rounds;
-                w.ncand = 0;
-                confl = LONG ? cs_scan_long(w) : cs_scan_short(w);
-                if (confl < 0) confl = cs_scan_learned(w);
-                if (confl >= 0) {   // nothing is implied in this round
-                    for (int i = ln; i < w.ncand; i += 64) w.reason[w.trail[w.trail_len + i] & 0x7FFFu] = CS_NONE;
-                    w.ncand = 0;
-                    wave_sync();
-                    break;
-                }
-                if (w.ncand == 0) break;   // the fixpoint
-                for (int i = ln; i < w.ncand; i += 64) {
-                    const uint16_t e = w.trail[w.trail_len + i];
-                    const uint32_t v = e & 0x7FFFu;
-                    w.flags[v] = (uint8_t)((w.flags[v] & 12u) | ((e & 0x8000u) ? 2u : 1u));
-                    w.level[v] = (uint16_t)w.cur;
-                }
-                w.trail_len += w.ncand;
-                props += w.ncand;
-                wave_sync();
-            }
-            const bool late = A.time_limit_ticks && __builtin_amdgcn_s_memrealtime() - t0 > A.time_limit_ticks;
-            if (confl >= 0) {
-                ++conflicts;
-                if (w.cur == 0) {   // UNSAT: the empty clause closes the proof
-                    ++records;
-                    ++words;
-                    if (w.used + 1 <= w.room) {
-                        if (ln == 0) w.rec[w.used] = 0;
-                        ++w.used;
-                        status = SATMI_CDCL_SOUND_UNSAT;
-                    } else {
-                        status = SATMI_CDCL_SOUND_FULL;
-                    }
-                    break;
-                }
-                if ((A.conflict_limit > 0 && conflicts >= A.conflict_limit) || late) {
-                    status = SATMI_CDCL_SOUND_LIMIT;
-                    break;
-                }
-                // ---- first-UIP analysis, backwards over the trail
-                int counter = 0, nlow = 0, idx = w.trail_len - 1;
-                uint32_t pvar = 0;
-                uint16_t pe = 0;
-                int code = confl;
-                bool broken = false;
-                for (int step = 0; step <= w.trail_len; ++step) {
-                    int len;
-                    const int32_t *p = cs_clause(w, code, &len);
-                    for (int j0 = 0; j0 < len; j0 += 64) {
-                        const int j = j0 + ln;
-                        bool at_cur = false, low = false;
-                        if (j < len) {
-                            const uint32_t v = cs_var(p[j]);
-                            const int lv = w.level[v];
-                            if (v != pvar && lv > 0) {
-                                const uint32_t bit = 1u << (v & 31u);
-                                if (!(atomicOr(&w.seen[v >> 5], bit) & bit)) {   // this lane marked it
-                                    at_cur = lv == w.cur;
-                                    low = !at_cur;
-                                }
-                            }
-                        }
-                        counter += __popcll(__ballot(at_cur));
-                        nlow += __popcll(__ballot(low));
-                    }
-                    wave_sync();
-                    // the next marked literal down the trail
-                    bool found = false;
-                    for (; idx >= 0 && !found;) {
-                        const int i = idx - ln;
-                        const uint64_t sm = __ballot(i >= 0 && cs_seen(w, w.trail[i] & 0x7FFFu));
-                        if (sm) {
-                            idx -= (int)__builtin_ctzll(sm);
-                            found = true;
-                        } else {
-                            idx -= 64;
-                        }
-                    }
-                    if (!found) {
-                        broken = true;
-                        break;
-                    }
-                    pe = (uint16_t)uniform_i32(w.trail[idx]);
-                    pvar = pe & 0x7FFFu;
-                    if (ln == 0) atomicAnd(&w.seen[pvar >> 5], ~(1u << (pvar & 31u)));
-                    wave_sync();
-                    --idx;
-                    --counter;
-                    if (counter <= 0) break;
-                    code = uniform_i32(w.reason[pvar]);
-                    if (code < 0 || code == CS_NONE) {   // a decision with marks above it: never by the rule
-                        broken = true;
-                        break;
-                    }
-                }
-                if (broken || counter != 0) {
-                    status = SATMI_CDCL_SOUND_LIMIT;
-                    break;
-                }
-                // ---- the learned clause: the asserting literal, then the others down the trail
-                const int len = 1 + nlow;
-                const int64_t need = 1 + (int64_t)len;
-                ++records;
-                words += need;
-                if (w.used + need > w.room || (int64_t)w.m + w.used + need > (int64_t)INT32_MAX) {
-                    status = SATMI_CDCL_SOUND_FULL;   // nothing of the record is written
-                    break;
-                }
-                int32_t *rp = w.rec + w.used;
-                if (ln == 0) {
-                    rp[0] = len;
-                    rp[1] = -cs_dec(pe);
-                    ++w.act[pvar];
-                }
-                int k = 0, bj = 0;
-                for (; idx >= 0 && k < nlow; idx -= 64) {
-                    const int i = idx - ln;
-                    bool s = false;
-                    uint16_t e = 0;
-                    int lv = 0;
-                    if (i >= 0) {
-                        e = w.trail[i];
-                        const uint32_t v = e & 0x7FFFu;
-                        s = cs_seen(w, v);
-                        lv = w.level[v];
-                    }
-                    const uint64_t sm = __ballot(s);
-                    if (sm && k == 0) bj = __builtin_amdgcn_readlane(lv, (int)__builtin_ctzll(sm));
-                    if (s) {
-                        const uint32_t v = e & 0x7FFFu;
-                        const int at = k + __popcll(sm & lt);
-                        atomicAnd(&w.seen[v >> 5], ~(1u << (v & 31u)));
-                        if (at < nlow) rp[2 + at] = -cs_dec(e);   // (every mark is on the trail once: always so)
-                        ++w.act[v];
-                    }
-                    k += __popcll(sm);
-                }
-                w.used += need;
-                ++learned;
-                learned_lits += len;
-                // ---- backjump: the trail's levels ascend, so what stays is a prefix
-                int keep_n = 0;
-                for (int i0 = 0; i0 < w.trail_len; i0 += 64) {
-                    const int i = i0 + ln;
-                    bool keep = false;
-                    if (i < w.trail_len) {
-                        const uint32_t v = w.trail[i] & 0x7FFFu;
-                        keep = w.level[v] <= bj;
-                        if (!keep) {
-                            const uint32_t f = w.flags[v];
-                            w.flags[v] = (uint8_t)((f & 8u) | ((f & 3u) == 1u ? 4u : 0u));   // unassigned, its phase saved
-                            w.reason[v] = CS_NONE;
-                        }
-                    }
-                    keep_n += __popcll(__ballot(keep));
-                }
-                w.trail_len = keep_n;
-                w.cur = bj;
-                if ((conflicts & 255) == 0)
-                    for (int v = 1 + ln; v <= w.nv; v += 64) w.act[v] >>= 1;
-                wave_sync();
-                continue;
-            }
-            // ---- decide: the unassigned variable of the formula with the highest activity, the lowest id on a tie
-            uint32_t best = 0;
-            for (int v0 = 1; v0 <= w.nv; v0 += 64) {
-                const int v = v0 + ln;
-                if (v <= w.nv) {
-                    const uint32_t f = w.flags[v];
-                    if ((f & 8u) && !(f & 3u)) best = max(best, ((uint32_t)w.act[v] << 15) | (uint32_t)(32767 - v));
-                }
-            }
-            best = wave_max_u32(best);
-            if (best == 0u) {   // SAT: every variable of the formula is assigned
-                int k = 0;
-                for (int v0 = 1; v0 <= w.nv; v0 += 64) {
-                    const int v = v0 + ln;
-                    const uint32_t f = v <= w.nv ? w.flags[v] : 0u;
-                    const bool occ = (f & 8u) != 0u;
-                    const uint64_t om = __ballot(occ);
-                    const int at = k + __popcll(om & lt);
-                    if (occ && at < A.stride) A.row_lits[b * A.stride + at] = (f & 3u) == 1u ? v : -v;
-                    k += __popcll(om);
-                }
-                row = k;
-                status = SATMI_CDCL_SOUND_SAT;
-                break;
-            }
-            if (late) {
-                status = SATMI_CDCL_SOUND_LIMIT;
-                break;
-            }
-            {
-                const uint32_t v = 32767u - (best & 32767u);
-                ++w.cur;
-                ++decisions;
-                top = max(top, (int64_t)w.cur);
-                if (ln == 0) {
-                    const uint32_t f = w.flags[v];
-                    w.flags[v] = (uint8_t)(f | ((f & 4u) ? 1u : 2u));
-                    w.level[v] = (uint16_t)w.cur;
-                    w.reason[v] = -1;
-                    w.trail[w.trail_len] = (uint16_t)(v | ((f & 4u) ? 0u : 0x8000u));
-                }
-                ++w.trail_len;
-                wave_sync();
-            }
-        }
-        if (status == CS_RUNNING) status = SATMI_CDCL_SOUND_LIMIT;   // the pass bound (never by the rule)
-        const bool trunc = status == SATMI_CDCL_SOUND_FULL;
-        if (ln == 0) {
-            A.status[b] = status;
-            A.row_len[b] = row;
-        }
-        if (ln < SATMI_CDCL_SOUND_NCOUNTERS)
-            A.counters[b * SATMI_CDCL_SOUND_NCOUNTERS + ln] = ln == 0   ? conflicts
-                                                              : ln == 1 ? decisions
-                                                              : ln == 2 ? props
-                                                              : ln == 3 ? rounds
-                                                              : ln == 4 ? learned
-                                                              : ln == 5 ? learned_lits
-                                                              : ln == 6 ? top
-                                                                        : 0;
-        if (ln < SATMI_CDCL_SOUND_NWORDS)
-            A.info[b * SATMI_CDCL_SOUND_NWORDS + ln] = ln == 0   ? records
-                                                       : ln == 1 ? words
-                                                       : ln == 2 ? (trunc ? SATMI_CDCL_SOUND_TRUNCATED : 0)
-                                                                 : 0;
-        wave_sync();
-    }
-}
-
 // ------------------------------------------------------------------ the pack
 // The lemma regions of a solve as the proof triple of the refutation check.
 // An instance contributes its records when it ended UNSAT (its region then holds
@@ -522,9 +245,14 @@ struct CsPack {
     int num_instances;
 };
 
+// (ASSUMED: the pack of the assumption-carrying solve, where an instance that
+// ended ASSUMED contributes too: its region is closed like an UNSAT one's.)
+template <bool ASSUMED>
 __device__ __forceinline__ void cs_contribution(const CsPack &P, int b, int64_t *n, int64_t *l) {
     const int64_t *w = P.info + (int64_t)b * SATMI_CDCL_SOUND_NWORDS;
-    const bool whole = P.status[b] == SATMI_CDCL_SOUND_UNSAT && !(w[2] & SATMI_CDCL_SOUND_TRUNCATED);
+    const int32_t st = P.status[b];
+    const bool whole = (st == SATMI_CDCL_SOUND_UNSAT || (ASSUMED && st == SATMI_CDCL_SOUND_ASSUMED)) &&
+                       !(w[2] & SATMI_CDCL_SOUND_TRUNCATED);
     *n = whole ? w[0] : 0;
     *l = whole ? w[1] - w[0] : 0;
 }
@@ -538,40 +266,28 @@ __device__ __forceinline__ int64_t cs_incl_scan64(int64_t x) {
     return x;
 }
 
-// One wavefront: the totals, whether they fit, and the offsets by an exclusive
-// scan, 64 instances at a time.  Totals that do not fit leave every instance
-// with no lemma, as dpll_proof.hip's pack does.
-__global__ void __launch_bounds__(64) cdcl_sound_pack_scan_kernel(CsPack P) {
-    const int ln = lane_id(), B = P.num_instances;
-    int64_t sn = 0, sl = 0;
-    for (int b = ln; b < B; b += 64) {
-        int64_t n, l;
-        cs_contribution(P, b, &n, &l);
-        sn += n;
-        sl += l;
-    }
-    const int64_t tn = __shfl(cs_incl_scan64(sn), 63, 64), tl = __shfl(cs_incl_scan64(sl), 63, 64);
-    const bool fits = tn <= P.clause_cap && tl <= P.lit_cap && tn <= INT32_MAX - 1 && tl <= INT32_MAX;
-    if (ln == 0) {
-        P.totals[0] = tn;
-        P.totals[1] = tl;
-        P.pib[B] = fits ? (int32_t)tn : 0;
-        P.pcb[fits ? tn : 0] = fits ? (int32_t)tl : 0;
-    }
-    int64_t cn = 0, cl = 0;
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int b = b0 + ln;
-        int64_t n = 0, l = 0;
-        if (b < B) cs_contribution(P, b, &n, &l);
-        const int64_t in = cs_incl_scan64(n), il = cs_incl_scan64(l);
-        if (b < B) {
-            P.pib[b] = fits ? (int32_t)(cn + in - n) : 0;
-            P.info[(int64_t)b * SATMI_CDCL_SOUND_NWORDS + 3] = fits ? cl + il - l : 0;
-        }
-        cn += __shfl(in, 63, 64);
-        cl += __shfl(il, 63, 64);
-    }
-}
+// ------------------------------------------------------------------ the kernels
+// The search and the pack's scan, in both forms: cdcl_sound_search.inc is their
+// text.  The first inclusion gives the kernels of satmi_cdcl_sound_* as they
+// always were; the second the assumption-carrying ones of satmi_cdcl_assume_*.
+#define CS_ASSUME 0
+#define CS_SEARCH_KERNEL cdcl_sound_kernel
+#define CS_SEARCH_ARGS CsArgs
+#define CS_PACK_SCAN_KERNEL cdcl_sound_pack_scan_kernel
+#include "cdcl_sound_search.inc"
+#undef CS_ASSUME
+#undef CS_SEARCH_KERNEL
+#undef CS_SEARCH_ARGS
+#undef CS_PACK_SCAN_KERNEL
+#define CS_ASSUME 1
+#define CS_SEARCH_KERNEL cdcl_assume_kernel
+#define CS_SEARCH_ARGS CsAssumeArgs
+#define CS_PACK_SCAN_KERNEL cdcl_assume_pack_scan_kernel
+#include "cdcl_sound_search.inc"
+#undef CS_ASSUME
+#undef CS_SEARCH_KERNEL
+#undef CS_SEARCH_ARGS
+#undef CS_PACK_SCAN_KERNEL
 
 // One wavefront per instance, record after record.
 __global__ void __launch_bounds__(256) cdcl_sound_pack_copy_kernel(CsPack P) {
@@ -600,6 +316,7 @@ __global__ void __launch_bounds__(256) cdcl_sound_pack_copy_kernel(CsPack P) {
 namespace {
 
 constexpr OomText CS_OOM{"satmi_cdcl_sound_batch_host", "split the batch"};
+constexpr OomText CS_ASSUME_OOM{"satmi_cdcl_assume_batch_host", "split the batch"};
 
 std::atomic<int> g_cs_grid{0}, g_cs_wpg{0};      // satmi_cdcl_sound_debug_grid
 std::atomic<int64_t> g_cs_room{0};               // satmi_cdcl_sound_debug_room
@@ -640,20 +357,30 @@ extern "C" int satmi_cdcl_sound_debug_room(int64_t words) {
     return SATMI_OK;
 }
 
-extern "C" int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
-                                             const int32_t *d_clause_lit_begin, const int32_t *d_lits,
-                                             const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
-                                             int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
-                                             const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
-                                             int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
-                                             void *stream) {
-    const char *who = "satmi_cdcl_sound_batch_device";
+namespace {
+
+// The assumption arrays and core outputs of the satmi_cdcl_assume_* forms.
+struct CsAssumeIo {
+    const int32_t *begin, *lits;
+    int32_t *core_len, *core_lits;
+    int core_stride;
+};
+
+// Both device forms: `as` = nullptr is satmi_cdcl_sound_batch_device, its kernels and all.
+int cs_solve_device(const char *who, const CsAssumeIo *as, int num_instances, const int32_t *d_inst_clause_begin,
+                    const int32_t *d_clause_lit_begin, const int32_t *d_lits, const int32_t *d_inst_nvars,
+                    int max_vars, int max_clause_len, int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                    const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters, int32_t *d_row_len,
+                    int32_t *d_row_lits, int stride, int64_t *d_info, void *stream) {
     if (num_instances < 0) return fail_arg(who, "negative formula count");
     if (max_vars < 0 || max_clause_len < 0) return fail_arg(who, "negative max_vars / max_clause_len");
     if (stride < 1) return fail_arg(who, "row stride < 1");
+    if (as && as->core_stride < 0) return fail_arg(who, "negative core_stride");
     if (num_instances == 0) return SATMI_OK;
     if (!d_inst_clause_begin || !d_clause_lit_begin || !d_lits || !d_inst_nvars || !d_lemmas || !d_lemma_begin ||
         !d_status || !d_counters || !d_row_len || !d_row_lits || !d_info)
+        return fail_arg(who, "null pointer");
+    if (as && (!as->begin || !as->lits || !as->core_len || (as->core_stride > 0 && !as->core_lits)))
         return fail_arg(who, "null pointer");
     if (max_vars > SATMI_CDCL_SOUND_MAX_VARS) return cs_too_large(who, max_vars);
     DeviceFacts facts;
@@ -696,6 +423,23 @@ extern "C" int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d
     const int grid = batch_grid(facts, lds_bytes, 0, 64 * wpg, wgs, g_cs_grid);
     const bool long_form = max_clause_len <= 0 || max_clause_len > CS_SHORT_MAX;
     hipStream_t s = (hipStream_t)stream;
+    if (as) {
+        CsAssumeArgs AA{};
+        static_cast<CsArgs &>(AA) = A;
+        AA.assume_begin = as->begin;
+        AA.assume_lits = as->lits;
+        AA.core_len = as->core_len;
+        AA.core_lits = as->core_lits;
+        AA.core_stride = as->core_stride;
+        const void *fn = long_form ? (const void *)cdcl_assume_kernel<true> : (const void *)cdcl_assume_kernel<false>;
+        SATMI_TRY(batch_allow_lds(fn, lds_bytes));
+        if (long_form)
+            hipLaunchKernelGGL(cdcl_assume_kernel<true>, dim3(grid), dim3(64 * wpg), lds_bytes, s, AA);
+        else
+            hipLaunchKernelGGL(cdcl_assume_kernel<false>, dim3(grid), dim3(64 * wpg), lds_bytes, s, AA);
+        SATMI_HIP(hipGetLastError());
+        return SATMI_OK;
+    }
     const void *fn = long_form ? (const void *)cdcl_sound_kernel<true> : (const void *)cdcl_sound_kernel<false>;
     SATMI_TRY(batch_allow_lds(fn, lds_bytes));
     if (long_form)
@@ -706,12 +450,11 @@ extern "C" int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d
     return SATMI_OK;
 }
 
-extern "C" int satmi_cdcl_sound_pack_device(int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
-                                            const int64_t *d_lemma_begin, int64_t *d_info,
-                                            int32_t *d_proof_inst_begin, int32_t *d_proof_clause_begin,
-                                            int64_t proof_clause_cap, int32_t *d_proof_lits, int64_t proof_lit_cap,
-                                            int64_t *d_totals, void *stream) {
-    const char *who = "satmi_cdcl_sound_pack_device";
+// Both packs: `assumed` = an instance that ended ASSUMED has its lemmas in the proof too.
+int cs_pack_device(const char *who, bool assumed, int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
+                   const int64_t *d_lemma_begin, int64_t *d_info, int32_t *d_proof_inst_begin,
+                   int32_t *d_proof_clause_begin, int64_t proof_clause_cap, int32_t *d_proof_lits,
+                   int64_t proof_lit_cap, int64_t *d_totals, void *stream) {
     if (num_instances < 0) return fail_arg(who, "negative formula count");
     if (proof_clause_cap < 1 || proof_lit_cap < 1) return fail_arg(who, "non-positive proof capacity");
     if (num_instances == 0) return SATMI_OK;
@@ -731,7 +474,10 @@ extern "C" int satmi_cdcl_sound_pack_device(int num_instances, const int32_t *d_
     P.totals = d_totals;
     P.num_instances = num_instances;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(cdcl_sound_pack_scan_kernel, dim3(1), dim3(64), 0, s, P);
+    if (assumed)
+        hipLaunchKernelGGL(cdcl_assume_pack_scan_kernel, dim3(1), dim3(64), 0, s, P);
+    else
+        hipLaunchKernelGGL(cdcl_sound_pack_scan_kernel, dim3(1), dim3(64), 0, s, P);
     SATMI_HIP(hipGetLastError());
     const int wgs = std::min((num_instances + 3) / 4, 8192);
     hipLaunchKernelGGL(cdcl_sound_pack_copy_kernel, dim3(wgs), dim3(256), 0, s, P);
@@ -739,24 +485,77 @@ extern "C" int satmi_cdcl_sound_pack_device(int num_instances, const int32_t *d_
     return SATMI_OK;
 }
 
-extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
-                                           const int32_t *h_clause_lit_begin, const int32_t *h_lits,
-                                           const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
-                                           int64_t room_cap, int32_t *h_status, int64_t *h_counters,
-                                           int32_t *h_row_len, int32_t *h_row_lits, int stride,
-                                           int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
-                                           int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
-                                           int64_t *h_info, int64_t *h_totals) {
-    const char *who = "satmi_cdcl_sound_batch_host";
+}  // namespace
+
+extern "C" int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                             const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                             const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                             int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                             const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                             int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                             void *stream) {
+    return cs_solve_device("satmi_cdcl_sound_batch_device", nullptr, num_instances, d_inst_clause_begin,
+                           d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
+                           time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
+                           d_info, stream);
+}
+
+extern "C" int satmi_cdcl_assume_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                              const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                              const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                              int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                              const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                              int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                              const int32_t *d_assume_begin, const int32_t *d_assume_lits,
+                                              int32_t *d_core_len, int32_t *d_core_lits, int core_stride,
+                                              void *stream) {
+    const CsAssumeIo as{d_assume_begin, d_assume_lits, d_core_len, d_core_lits, core_stride};
+    return cs_solve_device("satmi_cdcl_assume_batch_device", &as, num_instances, d_inst_clause_begin,
+                           d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
+                           time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
+                           d_info, stream);
+}
+
+extern "C" int satmi_cdcl_sound_pack_device(int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
+                                            const int64_t *d_lemma_begin, int64_t *d_info,
+                                            int32_t *d_proof_inst_begin, int32_t *d_proof_clause_begin,
+                                            int64_t proof_clause_cap, int32_t *d_proof_lits, int64_t proof_lit_cap,
+                                            int64_t *d_totals, void *stream) {
+    return cs_pack_device("satmi_cdcl_sound_pack_device", false, num_instances, d_status, d_lemmas, d_lemma_begin,
+                          d_info, d_proof_inst_begin, d_proof_clause_begin, proof_clause_cap, d_proof_lits,
+                          proof_lit_cap, d_totals, stream);
+}
+
+extern "C" int satmi_cdcl_assume_pack_device(int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
+                                             const int64_t *d_lemma_begin, int64_t *d_info,
+                                             int32_t *d_proof_inst_begin, int32_t *d_proof_clause_begin,
+                                             int64_t proof_clause_cap, int32_t *d_proof_lits, int64_t proof_lit_cap,
+                                             int64_t *d_totals, void *stream) {
+    return cs_pack_device("satmi_cdcl_assume_pack_device", true, num_instances, d_status, d_lemmas, d_lemma_begin,
+                          d_info, d_proof_inst_begin, d_proof_clause_begin, proof_clause_cap, d_proof_lits,
+                          proof_lit_cap, d_totals, stream);
+}
+
+namespace {
+
+// Both host forms: `as` = nullptr is satmi_cdcl_sound_batch_host, else its host arrays.
+int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int num_instances,
+                  const int32_t *h_inst_clause_begin, const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                  const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s, int64_t room_cap,
+                  int32_t *h_status, int64_t *h_counters, int32_t *h_row_len, int32_t *h_row_lits, int stride,
+                  int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin, int64_t proof_clause_cap,
+                  int32_t *h_proof_lits, int64_t proof_lit_cap, int64_t *h_info, int64_t *h_totals) {
     // ---- check: all of it before any HIP call
     CsrShape sh;
     std::vector<int32_t> nv((size_t)std::max(num_instances, 0));
     const char *own = proof_clause_cap < 1 || proof_lit_cap < 1 ? "non-positive proof capacity"
                       : room_cap < 0                            ? "negative room_cap"
                       : stride < 1                              ? "row stride < 1"
+                      : as && as->core_stride < 0               ? "negative core_stride"
                                                                 : nullptr;
     const bool outs = h_inst_nvars && h_status && h_counters && h_row_len && h_row_lits && h_proof_inst_begin &&
-                      h_proof_clause_begin && h_proof_lits && h_totals;
+                      h_proof_clause_begin && h_proof_lits && h_totals &&
+                      (!as || (as->begin && as->core_len && (as->core_stride == 0 || as->core_lits)));
     if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits, own, outs,
                                           &sh, nv.data()))
         return fail_arg(who, bad);
@@ -771,6 +570,20 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
     if (stride < max_vars) return fail_arg(who, "row stride < number of variables");
     if (proof_clause_cap > INT32_MAX - 1 || proof_lit_cap > INT32_MAX)
         return fail_arg(who, "proof capacity beyond the 32-bit offsets of the proof arrays");
+    int Atot = 0;
+    if (as) {   // the assumption ranges, as satmi_dpll_batch_host checks its init ranges
+        if (as->begin[0] < 0) return fail_arg(who, "assumption ranges are not ascending");
+        for (int b = 0; b < num_instances; ++b)
+            if (as->begin[b + 1] < as->begin[b]) return fail_arg(who, "assumption ranges are not ascending");
+        Atot = as->begin[num_instances];
+        if (Atot > 0 && !as->lits) return fail_arg(who, "null pointer");
+        for (int b = 0; b < num_instances; ++b)
+            for (int i = as->begin[b]; i < as->begin[b + 1]; ++i) {
+                const int32_t x = as->lits[i];
+                if (x == 0 || x == INT32_MIN) return fail_arg(who, "assumption literal 0 / INT32_MIN");
+                if (std::abs(x) > h_inst_nvars[b]) return fail_arg(who, "assumption literal beyond inst_nvars");
+            }
+    }
     if (max_vars > SATMI_CDCL_SOUND_MAX_VARS) return cs_too_large(who, max_vars);
 
     // ---- lease the workspace
@@ -801,13 +614,26 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
     const size_t o_pib = cv.take(4 * (B + 1));
     const size_t o_pcb = cv.take(4 * ((size_t)proof_clause_cap + 1));
     const size_t o_plits = cv.take(4 * (size_t)proof_lit_cap);
-    SATMI_TRY(wk.block.reserve(cv.at, &CS_OOM));
+    const size_t cstride = as ? (size_t)as->core_stride : 0;
+    const size_t o_ab = as ? cv.take(4 * (B + 1)) : 0;
+    const size_t o_al = as ? cv.take(4 * (size_t)std::max(Atot, 1)) : 0;
+    const size_t o_cl = as ? cv.take(4 * B) : 0;
+    const size_t o_core = as ? cv.take(4 * std::max<size_t>(B * cstride, 1)) : 0;
+    SATMI_TRY(wk.block.reserve(cv.at, oom));
     const Staged d{wk.block.as<unsigned char>(), s};
     SATMI_TRY(d.up(o_icb, h_inst_clause_begin, 4 * (B + 1)));
     SATMI_TRY(d.up(o_clb, h_clause_lit_begin, 4 * (size_t)(C + 1)));
     SATMI_TRY(d.up(o_lits, h_lits, 4 * (size_t)Ltot));
     SATMI_TRY(d.up(o_nv, h_inst_nvars, 4 * B));
     SATMI_HIP(hipMemsetAsync(d.at<int32_t>(o_row), 0, 4 * B * (size_t)stride, s));   // the words behind a row's length read 0
+    CsAssumeIo das{};
+    if (as) {
+        SATMI_TRY(d.up(o_ab, as->begin, 4 * (B + 1)));
+        SATMI_TRY(d.up(o_al, as->lits, 4 * (size_t)Atot));
+        if (cstride) SATMI_HIP(hipMemsetAsync(d.at<int32_t>(o_core), 0, 4 * B * cstride, s));   // likewise behind a core's length
+        das = CsAssumeIo{d.at<const int32_t>(o_ab), d.at<const int32_t>(o_al), d.at<int32_t>(o_cl),
+                         d.at<int32_t>(o_core), as->core_stride};
+    }
 
     // ---- solve; again with four times the room for the instances that ended FULL, up to the caller's cap
     const int64_t dbg_room = g_cs_room.load();
@@ -820,9 +646,10 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
     for (int round = 0; round < 32; ++round) {
         lb[0] = 0;
         for (size_t b = 0; b < B; ++b) lb[b + 1] = lb[b] + room[b];
-        SATMI_TRY(wk.lemmas.reserve(4 * (size_t)std::max<int64_t>(lb[B], 1), &CS_OOM));
+        SATMI_TRY(wk.lemmas.reserve(4 * (size_t)std::max<int64_t>(lb[B], 1), oom));
         SATMI_TRY(d.up(o_lb, lb.data(), 8 * (B + 1)));
-        SATMI_TRY(satmi_cdcl_sound_batch_device(
+        SATMI_TRY(cs_solve_device(
+            as ? "satmi_cdcl_assume_batch_device" : "satmi_cdcl_sound_batch_device", as ? &das : nullptr,
             num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
             d.at<const int32_t>(o_nv), max_vars, C > 0 ? sh.max_len : 0, conflict_limit, time_limit_s,
             wk.lemmas.as<int32_t>(), d.at<const int64_t>(o_lb), d.at<int32_t>(o_st), d.at<int64_t>(o_ctr),
@@ -837,10 +664,11 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
             }
         if (!again) break;
     }
-    SATMI_TRY(satmi_cdcl_sound_pack_device(num_instances, d.at<const int32_t>(o_st), wk.lemmas.as<const int32_t>(),
-                                           d.at<const int64_t>(o_lb), d.at<int64_t>(o_info), d.at<int32_t>(o_pib),
-                                           d.at<int32_t>(o_pcb), proof_clause_cap, d.at<int32_t>(o_plits),
-                                           proof_lit_cap, d.at<int64_t>(o_tot), s));
+    SATMI_TRY(cs_pack_device(as ? "satmi_cdcl_assume_pack_device" : "satmi_cdcl_sound_pack_device", as != nullptr,
+                             num_instances, d.at<const int32_t>(o_st), wk.lemmas.as<const int32_t>(),
+                             d.at<const int64_t>(o_lb), d.at<int64_t>(o_info), d.at<int32_t>(o_pib),
+                             d.at<int32_t>(o_pcb), proof_clause_cap, d.at<int32_t>(o_plits), proof_lit_cap,
+                             d.at<int64_t>(o_tot), s));
     // ---- copy back
     int64_t totals[2] = {0, 0};
     SATMI_TRY(d.down(totals, o_tot, 16));
@@ -849,6 +677,10 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
     SATMI_TRY(d.down(h_row_len, o_rl, 4 * B));
     SATMI_TRY(d.down(h_row_lits, o_row, 4 * B * (size_t)stride));
     SATMI_TRY(d.down(h_proof_inst_begin, o_pib, 4 * (B + 1)));
+    if (as) {
+        SATMI_TRY(d.down(as->core_len, o_cl, 4 * B));
+        SATMI_TRY(d.down(as->core_lits, o_core, 4 * B * cstride));
+    }
     SATMI_HIP(hipStreamSynchronize(s));
     lease.ok = true;   // the stream is drained; the next call trusts nothing of the workspace
     const bool fits = totals[0] <= proof_clause_cap && totals[1] <= proof_lit_cap;
@@ -862,4 +694,37 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
     h_totals[1] = totals[1];
     if (wk.lemmas.cap > ((size_t)256 << 20)) wk.lemmas.release();   // large regions are not kept in the pool
     return SATMI_OK;
+}
+
+}  // namespace
+
+extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                           const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                           const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                           int64_t room_cap, int32_t *h_status, int64_t *h_counters,
+                                           int32_t *h_row_len, int32_t *h_row_lits, int stride,
+                                           int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
+                                           int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
+                                           int64_t *h_info, int64_t *h_totals) {
+    return cs_batch_host("satmi_cdcl_sound_batch_host", &CS_OOM, nullptr, num_instances, h_inst_clause_begin,
+                         h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
+                         h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
+                         proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
+}
+
+extern "C" int satmi_cdcl_assume_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                            const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                            const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                            int64_t room_cap, int32_t *h_status, int64_t *h_counters,
+                                            int32_t *h_row_len, int32_t *h_row_lits, int stride,
+                                            int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
+                                            int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
+                                            int64_t *h_info, int64_t *h_totals, const int32_t *h_assume_begin,
+                                            const int32_t *h_assume_lits, int32_t *h_core_len, int32_t *h_core_lits,
+                                            int core_stride) {
+    const CsAssumeIo as{h_assume_begin, h_assume_lits, h_core_len, h_core_lits, core_stride};
+    return cs_batch_host("satmi_cdcl_assume_batch_host", &CS_ASSUME_OOM, &as, num_instances, h_inst_clause_begin,
+                         h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
+                         h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
+                         proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
 }

@@ -53,7 +53,8 @@ DPLL_PROOF_WORDS = ("lemmas", "log_words", "flags", "first_literal")
 DPLL_PROOF_TRUNCATED = 1
 # satmi_cdcl_sound_*: the statuses, the int64 counters and info words per instance, the flags bit, the largest max_vars
 CDCL_SOUND_UNSAT, CDCL_SOUND_SAT, CDCL_SOUND_LIMIT, CDCL_SOUND_FULL, CDCL_SOUND_TOO_LARGE = range(5)
-CDCL_SOUND_STATUS_NAMES = {0: "unsat", 1: "sat", 2: "limit", 3: "full", 4: "too_large"}
+CDCL_SOUND_ASSUMED = 5   # satmi_cdcl_assume_*: UNSAT under the assumptions
+CDCL_SOUND_STATUS_NAMES = {0: "unsat", 1: "sat", 2: "limit", 3: "full", 4: "too_large", 5: "assumed"}
 CDCL_SOUND_NCOUNTERS = 8
 CDCL_SOUND_COUNTERS = ("conflicts", "decisions", "propagated", "rounds", "learned", "learned_literals",
                        "max_level", "restarts")
@@ -83,6 +84,7 @@ EXPORTED = (
     "satmi_dpll_refutations_device", "satmi_dpll_refutations_host", "satmi_dpll_refutations_debug_room",
     "satmi_cdcl_sound_batch_device", "satmi_cdcl_sound_pack_device", "satmi_cdcl_sound_batch_host",
     "satmi_cdcl_sound_debug_grid", "satmi_cdcl_sound_debug_room", "satmi_cdcl_sound_lds_bytes",
+    "satmi_cdcl_assume_batch_device", "satmi_cdcl_assume_pack_device", "satmi_cdcl_assume_batch_host",
 )
 
 
@@ -240,6 +242,14 @@ def load():
     L.satmi_cdcl_sound_batch_host.argtypes = (
         [ctypes.c_int] + [i32p] * 4 + [ctypes.c_int64, ctypes.c_double, ctypes.c_int64]
         + [i32p, i64p, i32p, i32p, ctypes.c_int] + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64, i64p, i64p])
+    L.satmi_cdcl_assume_batch_device.argtypes = (
+        [ctypes.c_int] + [vp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_double] + [vp] * 6
+        + [ctypes.c_int, vp] + [vp] * 4 + [ctypes.c_int, vp])
+    L.satmi_cdcl_assume_pack_device.argtypes = L.satmi_cdcl_sound_pack_device.argtypes
+    L.satmi_cdcl_assume_batch_host.argtypes = (
+        [ctypes.c_int] + [i32p] * 4 + [ctypes.c_int64, ctypes.c_double, ctypes.c_int64]
+        + [i32p, i64p, i32p, i32p, ctypes.c_int] + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64, i64p, i64p]
+        + [i32p] * 4 + [ctypes.c_int])
     L.satmi_cdcl_sound_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     L.satmi_cdcl_sound_debug_room.argtypes = [ctypes.c_int64]
     L.satmi_cdcl_sound_lds_bytes.restype = ctypes.c_uint64

@@ -105,6 +105,120 @@ def cdcl_sound_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_c
     _capi.check(rc, "satmi_cdcl_sound_batch_device")
 
 
+# ---- under assumptions (satmi_cdcl_assume_*): failed-assumption cores with proofs
+def pack_assumptions(assumptions, num_instances):
+    """Per-formula assumption lists -> (assume_begin int32 [B + 1], assume_lits int32, never
+    empty, the largest variable per formula int32 [B]).  None = no assumptions anywhere."""
+    lists = [[] for _ in range(num_instances)] if assumptions is None else [list(a) for a in assumptions]
+    if len(lists) != num_instances:
+        raise ValueError("assumptions must have one list of literals per formula")
+    begin = np.zeros(num_instances + 1, dtype=np.int32)
+    np.cumsum([len(a) for a in lists], out=begin[1:])
+    flat = [int(l) for a in lists for l in a]
+    if any(l == 0 or not -2 ** 31 < l < 2 ** 31 for l in flat):
+        raise ValueError("assumption literals must be nonzero and within int32 (INT32_MIN excluded)")
+    top = np.array([max([abs(int(l)) for l in a] + [0]) for a in lists], dtype=np.int32)
+    return begin, np.array(flat or [0], dtype=np.int32), top
+
+
+def cdcl_assume_packed(batch, assume_begin, assume_lits, conflict_limit=0, time_limit=0.0, room_cap=0, room=None,
+                       core_stride=None):
+    """satmi_cdcl_assume_batch_host on a CnfBatch whose inst_nvars cover the assumptions'
+    variables, formula b under assume_lits[assume_begin[b] : assume_begin[b + 1]] in that order.
+    Returns cdcl_sound_packed's six and (core_len int32 [B], core_lits int32 [B, core_stride]):
+    the failed assumptions of a formula that ended CDCL_SOUND_ASSUMED, whose lemmas are in the
+    proof batch like those of an UNSAT one.  `core_stride` defaults to the longest assumption
+    list, which holds every core."""
+    L = _capi.load()
+    _capi.require_gpu()
+    B = batch.num_instances
+    assume_begin = np.ascontiguousarray(assume_begin, dtype=np.int32)
+    assume_lits = np.ascontiguousarray(assume_lits, dtype=np.int32)
+    stride = max(1, int(batch.inst_nvars.max(initial=0)))
+    if core_stride is None:
+        core_stride = max(1, int(np.diff(assume_begin).max(initial=0)))
+    status = np.zeros(B, dtype=np.int32)
+    counters = np.zeros((B, _capi.CDCL_SOUND_NCOUNTERS), dtype=np.int64)
+    row_len = np.zeros(B, dtype=np.int32)
+    row_lits = np.zeros((B, stride), dtype=np.int32)
+    core_len = np.zeros(B, dtype=np.int32)
+    core_lits = np.zeros((B, max(core_stride, 1)), dtype=np.int32)
+    info = np.zeros((B, _capi.CDCL_SOUND_NWORDS), dtype=np.int64)
+    totals = np.zeros(2, dtype=np.int64)
+    pib = np.zeros(B + 1, dtype=np.int32)
+    ccap, lcap = room if room is not None else (max(1024, 64 * B), max(16384, 1024 * B))
+    i64 = ctypes.c_int64
+    while True:
+        pcb = np.zeros(ccap + 1, dtype=np.int32)
+        plits = np.zeros(lcap, dtype=np.int32)
+        rc = L.satmi_cdcl_assume_batch_host(
+            B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits), _p(batch.inst_nvars),
+            int(conflict_limit), float(time_limit), int(room_cap), _p(status), _p(counters, i64), _p(row_len),
+            _p(row_lits), int(stride), _p(pib), _p(pcb), int(ccap), _p(plits), int(lcap), _p(info, i64),
+            _p(totals, i64), _p(assume_begin), _p(assume_lits), _p(core_len), _p(core_lits), int(core_stride))
+        _capi.check(rc, "satmi_cdcl_assume_batch_host")
+        if B == 0 or (int(totals[0]) <= ccap and int(totals[1]) <= lcap):
+            break
+        ccap, lcap = max(4 * ccap, int(totals[0])), max(4 * lcap, int(totals[1]))
+    P = int(pib[B]) if B else 0
+    proof = CnfBatch(pib, pcb[:P + 1].copy(), plits[:max(int(pcb[P]), 1)].copy(), np.zeros(B, dtype=np.int32))
+    return status, counters, row_len, row_lits, proof, info, core_len, core_lits[:, :core_stride]
+
+
+def cdcl_assume_batch(formulas, assumptions, conflict_limit=0, time_limit=0.0, room_cap=0, room=None,
+                      core_stride=None):
+    """Sound CDCL on `formulas` (a CnfBatch or a list of formulas), formula b under the literals
+    `assumptions[b]` in that order (None = none anywhere).  cdcl_sound_batch's dict per formula,
+    where "sat" is False for CDCL_SOUND_UNSAT and for CDCL_SOUND_ASSUMED (unsatisfiable under
+    the assumptions) alike and both carry "proof", the model is over the variables of formula
+    and assumptions, and "core" is the failed assumptions: the refuted one first, then those it
+    was refuted from ([] for UNSAT: the formula alone is refuted; None unless sat is False; the
+    first `core_stride` literals if that is given and smaller, "core_len" being the count
+    whatever was written).  refute.proof_of_cdcl_assumed
+    turns such a dict into the pair check_refutations takes."""
+    batch = formulas if isinstance(formulas, CnfBatch) else pack(formulas)
+    begin, lits, top = pack_assumptions(assumptions, batch.num_instances)
+    batch = CnfBatch(batch.inst_clause_begin, batch.clause_lit_begin, batch.lits,
+                     np.maximum(np.asarray(batch.inst_nvars, dtype=np.int32), top))
+    status, counters, row_len, row_lits, proof, info, core_len, core_lits = cdcl_assume_packed(
+        batch, begin, lits, conflict_limit, time_limit, room_cap, room, core_stride)
+    out = []
+    for b in range(batch.num_instances):
+        st = int(status[b])
+        sat = True if st == _capi.CDCL_SOUND_SAT else \
+            False if st in (_capi.CDCL_SOUND_UNSAT, _capi.CDCL_SOUND_ASSUMED) else None
+        out.append({"status": st, "sat": sat,
+                    "counters": dict(zip(_capi.CDCL_SOUND_COUNTERS, map(int, counters[b]))),
+                    "model": row_lits[b, :int(row_len[b])].tolist() if sat else None,
+                    "proof": [list(c) for c in proof.instance(b)] if sat is False else None,
+                    "core": core_lits[b, :int(core_len[b])].tolist() if sat is False else None,
+                    "core_len": int(core_len[b]),
+                    "records": int(info[b, 0]), "region_words": int(info[b, 1])})
+    return out
+
+
+def cdcl_assume_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clause_len, lemmas, lemma_begin,
+                       status, counters, row_len, row_lits, stride, info, assume_begin, assume_lits, core_len,
+                       core_lits, core_stride, conflict_limit=0, time_limit=0.0, stream=None):
+    """satmi_cdcl_assume_batch_device on device pointers (ints, e.g. a tensor's data_ptr());
+    asynchronous on `stream`."""
+    rc = _capi.load().satmi_cdcl_assume_batch_device(
+        int(num_instances), icb, clb, lits, inst_nvars, int(max_vars), int(max_clause_len), int(conflict_limit),
+        float(time_limit), lemmas, lemma_begin, status, counters, row_len, row_lits, int(stride), info,
+        assume_begin, assume_lits, core_len, core_lits, int(core_stride), stream)
+    _capi.check(rc, "satmi_cdcl_assume_batch_device")
+
+
+def assume_pack_device(num_instances, status, lemmas, lemma_begin, info, proof_icb, proof_clb, proof_clause_cap,
+                       proof_lits, proof_lit_cap, totals, stream=None):
+    """satmi_cdcl_assume_pack_device: pack_device for a cdcl_assume_device solve; the instances
+    that ended CDCL_SOUND_ASSUMED have their lemmas in the proof triple too."""
+    rc = _capi.load().satmi_cdcl_assume_pack_device(
+        int(num_instances), status, lemmas, lemma_begin, info, proof_icb, proof_clb, int(proof_clause_cap),
+        proof_lits, int(proof_lit_cap), totals, stream)
+    _capi.check(rc, "satmi_cdcl_assume_pack_device")
+
+
 def pack_device(num_instances, status, lemmas, lemma_begin, info, proof_icb, proof_clb, proof_clause_cap,
                 proof_lits, proof_lit_cap, totals, stream=None):
     """satmi_cdcl_sound_pack_device: the regions of a cdcl_sound_device solve as the proof triple

@@ -255,6 +255,21 @@ def proof_of_cdcl(r):
     return [list(c) for c in r["proof"]]
 
 
+def proof_of_cdcl_assumed(formula, r):
+    """The refutation in a cdcl_sound.cdcl_assume_batch dict that is unsatisfiable under its
+    assumptions, as the pair check_refutations / trim_refutations take: (the formula plus
+    the core's literals as unit clauses, the learned clauses in learning order, the empty
+    clause last).  Every lemma but the last follows from the formula alone; the empty clause
+    needs the core.  For a plain UNSAT answer the core is empty and the pair is the formula
+    and proof_of_cdcl's list.  Built on the host."""
+    if r.get("sat") is not False or r.get("proof") is None or r.get("core") is None:
+        raise ValueError("proof_of_cdcl_assumed: the search did not end UNSAT or unsatisfiable under its "
+                         "assumptions: it has no refutation")
+    if r.get("core_len", len(r["core"])) != len(r["core"]):
+        raise ValueError("proof_of_cdcl_assumed: the core was cut at core_stride")
+    return [list(c) for c in formula] + [[int(l)] for l in r["core"]], [list(c) for c in r["proof"]]
+
+
 def dpll_refutations_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clauses, max_lits,
                             max_clause_len, status, counters, sol_len, sol_lits, root_len, root_lits, sol_cap,
                             sol_stride, log, log_begin, proof_icb, proof_clb, proof_clause_cap, proof_lits,

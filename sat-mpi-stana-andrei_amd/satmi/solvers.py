@@ -238,22 +238,35 @@ def resolution_witness(formula: Formula) -> Tuple[bool, Optional[Assignment]]:
     return _witnesses([formula], [r], stages_of_resolution, True, "resolution_witness")[0]
 
 
-def cdcl_sound_solve(formula: Formula):
+def cdcl_sound_solve(formula: Formula, assumptions=None):
     """The library's own clause-learning decision procedure (csrc/cdcl_sound.hip):
     (True, model, None) with model {variable: bool} over the formula's variables, or
     (False, None, proof) where `proof` is the learned clauses in learning order, the empty
     clause last, and check_refutation(formula, proof) holds.  Raises SolverTimeout under the
     driver's deadline and SatmiError when the formula is beyond the kernel's layout or its
-    learned clauses outgrow their region."""
-    from .cdcl_sound import cdcl_sound_batch
+    learned clauses outgrow their region.
+    With `assumptions`, a list of literals (PySAT's solve(assumptions=...) and get_core()),
+    the question is whether the formula is satisfiable with all of them true, and the answer
+    has a fourth member: (True, model, None, None), the model over the assumptions' variables
+    too, or (False, None, proof, core), where `core` lists the assumptions to blame, the
+    refuted one first ([]: the formula alone is unsatisfiable), and check_refutation holds for
+    the formula plus the core's literals as unit clauses."""
+    from .cdcl_sound import cdcl_assume_batch, cdcl_sound_batch
     from .refute import proof_of_cdcl
-    r = cdcl_sound_batch([list(formula)], time_limit=_time_limit)[0]
+    if assumptions is not None:
+        r = cdcl_assume_batch([list(formula)], [list(assumptions)], time_limit=_time_limit)[0]
+    else:
+        r = cdcl_sound_batch([list(formula)], time_limit=_time_limit)[0]
     st = r["status"]
     if st == _capi.CDCL_SOUND_LIMIT:
         raise SolverTimeout(f"Timeout after {_time_limit:g} seconds")
     if r["sat"] is None:   # nothing was decided: never an UNSAT verdict
         raise _capi.SatmiError("cdcl_sound_solve: GPU search ended with status "
                                f"{_capi.CDCL_SOUND_STATUS_NAMES.get(st, st)}")
+    if assumptions is not None:
+        if r["sat"]:
+            return True, {abs(l): l > 0 for l in r["model"]}, None, None
+        return False, None, proof_of_cdcl(r), list(r["core"])
     if r["sat"]:
         return True, {abs(l): l > 0 for l in r["model"]}, None
     return False, None, proof_of_cdcl(r)
