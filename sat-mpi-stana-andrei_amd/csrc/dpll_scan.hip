@@ -52,11 +52,11 @@ namespace {
 #ifdef SATMI_PHASE_STAMPS
 struct PhaseClock {
     uint64_t acc[8];
-    uint64_t cnt[24];   // path counts (written after the clocks)
+    uint64_t cnt[28];   // path counts (written after the clocks)
     uint64_t t;
     __device__ void start() {
         for (int i = 0; i < 8; ++i) acc[i] = 0;
-        for (int i = 0; i < 24; ++i) cnt[i] = 0;
+        for (int i = 0; i < 28; ++i) cnt[i] = 0;
         t = __builtin_amdgcn_s_memtime();
     }
     __device__ void count(int i, uint64_t v = 1) { cnt[i] += v; }
@@ -823,10 +823,11 @@ __device__ int scan_counts(const SLds<K, C> &S, int mpad) {
 // The first flagged position (chunks in order, the scan stops at the first
 // chunk with a hit): the first flagged key in dict order.
 template <int K, typename C>
-__device__ uint32_t first_flagged(const SLds<K, C> &S, int mpad) {
+__device__ uint32_t first_flagged(const SLds<K, C> &S, int mpad, PhaseClock &ph) {
     using W = typename Pack<K>::W;
     const int ln = lane_id();
     for (int c0 = 0; c0 < mpad; c0 += 64) {
+        ph.count(24);
         const int c = c0 + ln;
         const W w = S.cls[c];
         uint32_t x[K], f[K];
@@ -888,8 +889,83 @@ struct Choice {
 // order matters: several variables share the largest count (the first of
 // them in dict order wins), or there are pure literals (their order is the
 // assignment's dict order).
+//
+// Byte codes (n <= 127: the bench kernel) read the variables once.  A sweep
+// step keeps one key per lane across the max reduction, (p + q) << 1 | pure
+// for a live variable and 0 for any other: the largest key holds the largest
+// count, the candidates are the lanes whose key >> 1 equals it, bit 0 is the
+// pure predicate, and the counts are cleared by the step that read them.  The
+// flags are written only where a position scan reads them (pure literals, a
+// tie).  Variable 0's counts need no clearing: padding slots add 0 to code 0,
+// and code 1 only fills dummy clauses, which are never active.
 template <int K, typename C>
-__device__ Choice choose(const SLds<K, C> &S, int n, int mpad) {
+__device__ Choice choose_bytes(const SLds<K, C> &S, int n, int mpad, PhaseClock &ph) {
+    static_assert(sizeof(C) == 1, "two sweep steps at most");
+    const int ln = lane_id_here();   // per call: lane-invariant addresses hoisted out of the node loop spill
+    const bool two = n >= 65;
+    // predicated (no exec-mask branches): lanes past n read and clear variable n's words
+    auto key_step = [&](int v0) -> uint32_t {
+        const int v = v0 + ln;
+        const uint32_t vc = (uint32_t)min(v, n);
+        const bool live = (v <= n) & var_free(S.lv, vc);
+        const uint2 c = cnt_pair(S, vc);   // the counts of codes 2v, 2v + 1
+        const uint32_t p = c.x, q = c.y;
+        cnt_clear_var(S, vc);   // cleared for the next scan
+        const uint32_t pure = ((p + q) != 0u) & ((p == 0u) | (q == 0u)) ? 1u : 0u;
+        return live ? (((p + q) << 1) | pure) : 0u;
+    };
+    const uint32_t ka = key_step(1);
+    uint32_t kb = 0u;
+    if (two) kb = key_step(65);
+    const int npure = __popcll(__ballot((ka & 1u) != 0u)) + __popcll(__ballot((kb & 1u) != 0u));
+    const uint32_t maxc = wave_max_u32(max(ka, kb)) >> 1;
+    // flags for the position scans (variable 0, the padding slots': never flagged)
+    auto put_flags = [&](auto &&flag) {
+        if (1 + ln <= n) S.first[1 + ln] = flag(ka);
+        if (65 + ln <= n) S.first[65 + ln] = flag(kb);
+        S.first[0] = 0u;
+        wave_sync();
+    };
+    uint32_t best = 0;
+    if (npure > 0) {
+        ph.count(25);
+        put_flags([](uint32_t k) { return (k & 1u) ? NONE32 : 0u; });
+        first_of_pures<K>(S, mpad, npure);
+        // plist in variable order; assign_pures ranks the entries by position
+        const uint64_t lt = lanemask_lt();
+        int k = 0;
+        auto collect = [&](int v0) {
+            const int v = v0 + ln;
+            const uint32_t f = v <= n ? S.first[v] : 0u;
+            const bool pure = f != 0u;
+            const uint64_t mk = __ballot(pure);
+            if (pure) S.plist[k + __popcll(mk & lt)] = f - 1u;
+            k += __popcll(mk);
+        };
+        collect(1);
+        if (two) collect(65);
+        wave_sync();
+    } else if (maxc > 0) {
+        // (a dead lane's key is 0: never a candidate of a largest count > 0)
+        const uint64_t ca = __ballot((ka >> 1) == maxc), cb = __ballot((kb >> 1) == maxc);
+        if (__popcll(ca) + __popcll(cb) == 1) {
+            best = ca ? 1u + (uint32_t)__builtin_ctzll(ca) : 65u + (uint32_t)__builtin_ctzll(cb);
+        } else {
+            ph.count(23);
+            ph.count(26, (uint64_t)(__popcll(ca) + __popcll(cb)));
+            put_flags([&](uint32_t k) { return (k >> 1) == maxc ? 1u : 0u; });
+            const uint32_t bestf = first_flagged<K>(S, mpad, ph);
+            best = uniform_u32(field<K>(S.cls[bestf >> 3], (int)(bestf & 7u)) >> 1);
+        }
+    }
+    return {npure, best};
+}
+
+template <int K, typename C>
+__device__ Choice choose(const SLds<K, C> &S, int n, int mpad, PhaseClock &ph) {
+    if constexpr (sizeof(C) == 1) {
+        return choose_bytes<K>(S, n, mpad, ph);
+    } else {
     const int ln = lane_id_here();   // per call: lane-invariant addresses hoisted out of the node loop spill
     const uint64_t lt = lanemask_lt();
     int npure = 0;
@@ -904,12 +980,7 @@ __device__ Choice choose(const SLds<K, C> &S, int n, int mpad) {
         lmax = live ? max(lmax, p + q) : lmax;
         npure += __popcll(__ballot(live & ((p + q) != 0u) & ((p == 0u) | (q == 0u))));
     };
-    if constexpr (sizeof(C) == 1) {   // byte trail codes: n <= 127, two steps at most, no loop
-        if (n >= 1) count_step(1);
-        if (n >= 65) count_step(65);
-    } else {
-        for (int v0 = 1; v0 <= n; v0 += 64) count_step(v0);
-    }
+    for (int v0 = 1; v0 <= n; v0 += 64) count_step(v0);
     const uint32_t maxc = wave_max_u32(lmax);
     int ncand = 0;
     uint32_t cvar = 0;   // the first candidate by variable index (the winner when it is the only one)
@@ -929,17 +1000,13 @@ __device__ Choice choose(const SLds<K, C> &S, int n, int mpad) {
         S.first[vw] = npure ? (pure ? NONE32 : 0u) : (cand ? 1u : 0u);
         cnt_clear_var(S, vw);   // cleared for the next scan
     };
-    if constexpr (sizeof(C) == 1) {
-        if (n >= 1) flag_step(1);
-        if (n >= 65) flag_step(65);
-    } else {
-        for (int v0 = 1; v0 <= n; v0 += 64) flag_step(v0);
-    }
+    for (int v0 = 1; v0 <= n; v0 += 64) flag_step(v0);
     cnt_clear_var(S, 0u);   // variable 0: the padding slots' counts (never read)
     S.first[0] = 0u;
     wave_sync();
     uint32_t best = 0;
     if (npure > 0) {
+        ph.count(25);
         first_of_pures<K>(S, mpad, npure);
         // plist in variable order; assign_pures ranks the entries by position
         int k = 0;
@@ -955,22 +1022,20 @@ __device__ Choice choose(const SLds<K, C> &S, int n, int mpad) {
             }
             k += __popcll(mk);
         };
-        if constexpr (sizeof(C) == 1) {
-            if (n >= 1) collect(1);
-            if (n >= 65) collect(65);
-        } else {
-            for (int v0 = 1; v0 <= n; v0 += 64) collect(v0);
-        }
+        for (int v0 = 1; v0 <= n; v0 += 64) collect(v0);
         wave_sync();
     } else if (maxc > 0) {
         if (ncand == 1) {
             best = cvar;
         } else {
-            const uint32_t bestf = first_flagged<K>(S, mpad);
+            ph.count(23);
+            ph.count(26, (uint64_t)ncand);
+            const uint32_t bestf = first_flagged<K>(S, mpad, ph);
             best = uniform_u32(field<K>(S.cls[bestf >> 3], (int)(bestf & 7u)) >> 1);
         }
     }
     return {npure, best};
+    }
 }
 
 // Append the pure literals in first-occurrence order (REF.py:187-189); the
@@ -1562,12 +1627,13 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
             bool leaf = false;
             Choice r{0, 0u};
             ph.mark(PH_OTHER);
+            ph.count(22);
             const int nact = scan_counts<K>(S, mpad);
             ph.mark(PH_COUNTS);
             if (nact == 0) {
                 leaf = true;                                   // REF.py:170-171
             } else {
-                r = choose<K>(S, n, mpad);
+                r = choose<K>(S, n, mpad, ph);
                 if (r.npure == 0 && r.best_var == 0u) leaf = true;   // REF.py:205-206
             }
             ph.mark(PH_CHOOSE);
@@ -1721,8 +1787,8 @@ __device__ bool solve_instance(const ScanArgs &A, const SLds<K, C> &S, int b, in
     }
 #ifdef SATMI_PHASE_STAMPS
     ph.mark(PH_OTHER);
-    // 8 clocks and 16 counts in a row of 48 words; a row of 64 takes all 24 counts
-    if (!is_task && A.root_lits && A.sol_stride >= 48 && ln < (A.sol_stride >= 64 ? 32 : 24))
+    // 8 clocks and 16 counts in a row of 48 words; a row of 64 takes 24 counts, one of 72 all 28
+    if (!is_task && A.root_lits && A.sol_stride >= 48 && ln < (A.sol_stride >= 72 ? 36 : A.sol_stride >= 64 ? 32 : 24))
         ((int64_t *)(A.root_lits + (int64_t)b * A.sol_stride))[ln] = (int64_t)(ln < 8 ? ph.acc[ln] : ph.cnt[ln - 8]);
 #endif
     if (SPLIT && status == STATUS_HANDED) return false;   // counters and ticks are in the row already

@@ -43,7 +43,7 @@ def main():
     ctr = torch.zeros((B, 8), dtype=torch.int64, device=dev)
     sl = torch.zeros(B, dtype=torch.int32, device=dev)
     so = torch.zeros((B, max(n, 16)), dtype=torch.int32, device=dev)
-    stride = max(n, 48)
+    stride = max(n, 72)
     root_len = torch.zeros(B, dtype=torch.int32, device=dev)
     root = torch.zeros((B, stride), dtype=torch.int32, device=dev)
     st = torch.cuda.current_stream(dev)
@@ -84,8 +84,8 @@ def main():
             out["rounds_per_node"] = float(c[:, 6].sum()) / nodes
             if kern in (_capi.KERNEL_SCAN, _capi.KERNEL_INC) and root.shape[1] >= 48:
                 # path counts of the incremental unit scan (csrc/dpll_scan.hip inc_units, diag build)
-                # (a row of 64 words or more carries all 24 counts, a shorter one the first 16)
-                nc = 24 if root.shape[1] >= 64 else 16
+                # (a row of 72 words or more carries all 28 counts, one of 64 the first 24, a shorter one 16)
+                nc = 28 if root.shape[1] >= 72 else 24 if root.shape[1] >= 64 else 16
                 cn = root[:, :2 * (8 + nc)].cpu().contiguous().view(torch.int64)[:, 8:8 + nc].double().sum(0)
                 cnames = ("unit_scans", "fast_one_step", "fast_conflict", "fast_few_units", "units_found",
                           "general", "fast_bitmap", "batch_literals", "general_batch_gt16", "general_touched_gt64",
@@ -93,8 +93,17 @@ def main():
                           # one-step rounds of 3+ units by batch size, the 2-unit rounds of a batch of one,
                           # and the 3+-unit rounds ranked by lane order
                           "many_units_batch1", "many_units_batch2", "many_units_batch3_4", "many_units_batch5up",
-                          "two_units_batch1", "lane_order_rounds")[:nc]
+                          "two_units_batch1", "lane_order_rounds",
+                          # the analysis (scan_counts + choose): analyses, those that end in a tie for the
+                          # largest count, the 64-clause chunks first_flagged walks for them, those that
+                          # find pure literals, the tied candidates (summed over the ties), one spare
+                          "analyses", "ties", "tie_chunks", "pure_analyses", "tie_candidates", "spare")[:nc]
                 out["per_node"] = {nm: float(cn[i]) / nodes for i, nm in enumerate(cnames)}
+                if nc >= 28 and cn[22] > 0:
+                    out["analysis"] = {"ties_per_analysis": float(cn[23] / cn[22]),
+                                       "pure_per_analysis": float(cn[25] / cn[22]),
+                                       "chunks_per_tie": float(cn[24] / cn[23]) if cn[23] > 0 else 0.0,
+                                       "candidates_per_tie": float(cn[26] / cn[23]) if cn[23] > 0 else 0.0}
         print(json.dumps(out), flush=True)
 
 

@@ -77,6 +77,15 @@ def main():
             table = json.load(fh)
     except (OSError, ValueError):
         table = {}
+    # the staleness key bench.py compares: the machine code of the launched kernel
+    # instance in the in-tree libsatmi.so (the library the profiled run shipped
+    # with); the instance's mangled-name substring carries over from the entry
+    # this one replaces
+    if entry["kernel"]:
+        sys.path.insert(0, os.path.join(ROOT, "sat-mpi-stana-andrei_amd"))
+        from satmi import isa
+        entry["isa_symbol"] = table.get(workload, {}).get("isa_symbol") or entry["kernel"].split("<")[0]
+        entry["kernel_isa_sha16"] = isa.kernel_code_sha(entry["isa_symbol"])
     table[workload] = entry
     with open(OUT, "w") as fh:
         json.dump(table, fh, indent=1, sort_keys=True)
