@@ -960,6 +960,105 @@ int satmi_cdcl_assume_batch_host(int num_instances, const int32_t *h_inst_clause
                                  const int32_t *h_assume_begin, const int32_t *h_assume_lits, int32_t *h_core_len,
                                  int32_t *h_core_lits, int core_stride);
 
+/*
+ * Incremental sound CDCL: the search above, started with lemmas that an earlier
+ * query on the same formula learned.  Every lemma of the assumption-carrying
+ * search follows from F alone, so it is still valid for the next query on F
+ * under other assumptions, and stays valid when clauses are added to F.
+ * satmi_cdcl_carry_batch_device (csrc/cdcl_sound.hip, a third instantiation of
+ * the search kernel; the ones above keep their machine code) takes and returns
+ * them where they lie, in the instance's region.  The assumption rule holds,
+ * with these additions; tests/cdcl_carry_rows.py restates them in Python.
+ *   Carried lemmas: carry_in[b] = (records, words), int64 [B x 2]: the first
+ *   `words` words of instance b's region hold `records` records
+ *   `len, lit_1 .. lit_len`, clauses that the caller asserts to follow from F.
+ *   They are the learned clauses m+0 .. m+p-1 in the order given, under the
+ *   reason codes already in place (m + word offset), and the clauses learned in
+ *   this call follow them.  From the first round on they are evaluated, offer
+ *   units, become conflicts and serve as reasons exactly as learned clauses do.
+ *   Their variables occur: they are decision candidates and are in the model
+ *   row.  A NULL carry_in carries nothing anywhere.
+ *   What is not carried: activities start at 0 and phases at False.  The
+ *   counters conflicts, learned and learned literals, and the conflict number
+ *   that conflict_limit and the halving look at, count this call only.  A
+ *   search that ended LIMIT and is resumed from its kept lemmas is therefore a
+ *   restart from level 0 with those lemmas.  Every output is a function of the
+ *   formula, the assumptions, conflict_limit and the carried list alone.
+ *   Empty carry: with no carried lemma every output equals
+ *   satmi_cdcl_assume_batch_*'s, word for word.
+ *   The proof: the region's records, the carried lemmas first and then, with
+ *   UNSAT or ASSUMED, the empty clause last, are the refutation of F plus the
+ *   core's unit clauses.  info[0] and info[1], the region's records and words,
+ *   count the carried ones too, so satmi_cdcl_assume_pack_device turns such a
+ *   region into the proof triple unchanged.  A carried list is an earlier
+ *   call's lemma sequence: each lemma is RUP from that call's formula and its
+ *   predecessors, hence from any formula that contains it and the same
+ *   predecessors; the lemmas of this call are RUP from F, the carried ones and
+ *   their own predecessors by the arguments above.
+ *   Who vouches for the carry: that a carried clause follows from F is the
+ *   caller's claim and the checker's verdict, not the solver's.  A carried
+ *   clause that does not follow from F can make a satisfiable F UNSAT; the
+ *   refutation check then fails at that lemma.
+ *   carry_out[b] = (records, words) of the non-empty records in the region at
+ *   the end: the carried ones and those learned and written, without the closing
+ *   empty record and without a record that did not fit (FULL).  It is what the
+ *   next query carries.  Only instance b's wavefront reads or writes entry b, so
+ *   carry_in and carry_out may be one array, and a chain of queries runs in
+ *   place on one stream with no copy and no pack in between.
+ *   Malformed carry: the instance ends SATMI_CDCL_SOUND_TOO_LARGE with the info
+ *   flag SATMI_CDCL_SOUND_BAD_CARRY, its region untouched and carry_out[b] =
+ *   (0, 0), when records or words is negative; the words exceed the region (or
+ *   m + words would pass 2^31 - 1); a record's length is below 1 (an empty
+ *   record is refused: the closing record of an earlier answer is never
+ *   carried); a record runs past the stated words, or the chain does not end
+ *   exactly on them after exactly the stated records; or a literal is 0,
+ *   INT32_MIN or beyond inst_nvars[b].  An instance that is TOO_LARGE for
+ *   another reason writes its carry_in back.
+ * satmi_cdcl_carry_pack_device packs every instance's kept lemmas, whatever its
+ * status, from `carry` (a carry_out) as a clause triple: instance b's clauses
+ * are kept_clause_begin[kept_inst_begin[b] .. kept_inst_begin[b + 1]]; totals
+ * [2] = lemmas and literals, and when they exceed a capacity (>= 0) no instance
+ * has a lemma and nothing is written past a capacity.  Counts that no region
+ * holds contribute nothing.
+ * The host form takes the carried lemmas as such a triple (h_carry_inst_begin
+ * [B + 1], h_carry_clause_begin, h_carry_lits; all three NULL: none) and
+ * returns the kept ones as one (the three arrays may be NULL with both
+ * capacities 0).  h_totals is [4]: proof lemmas, proof literals, kept lemmas,
+ * kept literals, the kept ones reported as the proof's are.  It checks all of
+ * it before any HIP call as satmi_cdcl_assume_batch_host does: the carry triple
+ * as a CSR pair, no empty clause, literals within inst_nvars[b] (a malformed
+ * carry is refused here, never launched).  Each region is the carried words
+ * plus the usual first room; a run-again starts from the input carry with four
+ * times the room, so the answer is the same whatever the first room was.  A
+ * room_cap below an instance's carried words refuses its carry (BAD_CARRY).
+ */
+#define SATMI_CDCL_SOUND_BAD_CARRY 2   /* flags bit: the carried records were malformed (with TOO_LARGE) */
+int satmi_cdcl_carry_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                  const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                  const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                  int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                  const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                  int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                  const int32_t *d_assume_begin, const int32_t *d_assume_lits, int32_t *d_core_len,
+                                  int32_t *d_core_lits, int core_stride, const int64_t *d_carry_in,
+                                  int64_t *d_carry_out, void *stream);
+int satmi_cdcl_carry_pack_device(int num_instances, const int32_t *d_lemmas, const int64_t *d_lemma_begin,
+                                 const int64_t *d_carry, int32_t *d_kept_inst_begin, int32_t *d_kept_clause_begin,
+                                 int64_t kept_clause_cap, int32_t *d_kept_lits, int64_t kept_lit_cap,
+                                 int64_t *d_totals, void *stream);
+int satmi_cdcl_carry_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                int64_t room_cap, int32_t *h_status, int64_t *h_counters, int32_t *h_row_len,
+                                int32_t *h_row_lits, int stride, int32_t *h_proof_inst_begin,
+                                int32_t *h_proof_clause_begin, int64_t proof_clause_cap, int32_t *h_proof_lits,
+                                int64_t proof_lit_cap, int64_t *h_info, int64_t *h_totals,
+                                const int32_t *h_assume_begin, const int32_t *h_assume_lits, int32_t *h_core_len,
+                                int32_t *h_core_lits, int core_stride, const int32_t *h_carry_inst_begin,
+                                const int32_t *h_carry_clause_begin, const int32_t *h_carry_lits,
+                                int32_t *h_kept_inst_begin, int32_t *h_kept_clause_begin, int64_t kept_clause_cap,
+                                int32_t *h_kept_lits, int64_t kept_lit_cap);
+
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into
  * d_span: [0] = ~(first wave's start), [1] = last wave's end, so the launch

@@ -39,6 +39,12 @@
 //     search with the final analysis, a walk down the trail along the reasons
 //     that collects the failed assumptions.  The search kernel and the pack's
 //     scan are compiled twice from cdcl_sound_search.inc, without and with it.
+//   * With carried lemmas (satmi_cdcl_carry_batch_device, restated in
+//     tests/cdcl_carry_rows.py) an instance starts with records in its region:
+//     the wave walks their chain once, refusing a malformed one before it
+//     touches anything, marks their variables as occurring and starts with
+//     `used` behind them; from then on they are learned clauses.  A third
+//     inclusion of the same text gives that search kernel.
 //
 // Plain C++ and vector memory operations only.  The translation unit shares no
 // device code with any other kernel, whose machine code stays what it is.
@@ -51,6 +57,7 @@
 #include <vector>
 
 #include "batch_host.h"
+#include "carry_records.h"
 #include "common.h"
 
 namespace satmi {
@@ -91,6 +98,14 @@ struct CsAssumeArgs : CsArgs {
     const int32_t *assume_begin, *assume_lits;
     int32_t *core_len, *core_lits;             // [B], [B x core_stride]
     int core_stride;
+};
+
+// The same with carried lemmas: instance b starts with carry_in[b] = (records,
+// words) in its region (nullptr: none anywhere) and ends with carry_out[b], the
+// non-empty records there.  Only wave b touches entry b: the two may be one array.
+struct CsCarryArgs : CsAssumeArgs {
+    const int64_t *carry_in;
+    int64_t *carry_out;                        // [B x 2]
 };
 
 struct CsWave {
@@ -269,8 +284,10 @@ __device__ __forceinline__ int64_t cs_incl_scan64(int64_t x) {
 // ------------------------------------------------------------------ the kernels
 // The search and the pack's scan, in both forms: cdcl_sound_search.inc is their
 // text.  The first inclusion gives the kernels of satmi_cdcl_sound_* as they
-// always were; the second the assumption-carrying ones of satmi_cdcl_assume_*.
+// always were; the second the assumption-carrying ones of satmi_cdcl_assume_*;
+// the third the search of satmi_cdcl_carry_*, which starts from carried lemmas.
 #define CS_ASSUME 0
+#define CS_CARRY 0
 #define CS_SEARCH_KERNEL cdcl_sound_kernel
 #define CS_SEARCH_ARGS CsArgs
 #define CS_PACK_SCAN_KERNEL cdcl_sound_pack_scan_kernel
@@ -285,9 +302,19 @@ __device__ __forceinline__ int64_t cs_incl_scan64(int64_t x) {
 #define CS_PACK_SCAN_KERNEL cdcl_assume_pack_scan_kernel
 #include "cdcl_sound_search.inc"
 #undef CS_ASSUME
+#undef CS_CARRY
 #undef CS_SEARCH_KERNEL
 #undef CS_SEARCH_ARGS
 #undef CS_PACK_SCAN_KERNEL
+#define CS_ASSUME 1
+#define CS_CARRY 1
+#define CS_SEARCH_KERNEL cdcl_carry_kernel
+#define CS_SEARCH_ARGS CsCarryArgs
+#include "cdcl_sound_search.inc"
+#undef CS_ASSUME
+#undef CS_CARRY
+#undef CS_SEARCH_KERNEL
+#undef CS_SEARCH_ARGS
 
 // One wavefront per instance, record after record.
 __global__ void __launch_bounds__(256) cdcl_sound_pack_copy_kernel(CsPack P) {
@@ -312,11 +339,107 @@ __global__ void __launch_bounds__(256) cdcl_sound_pack_copy_kernel(CsPack P) {
     }
 }
 
+// ------------------------------------------------------------------ the carry pack
+// The kept lemmas of a carrying solve as a clause triple: instance b's are the
+// first carry[2b] records, carry[2b + 1] words, of its region, whatever its
+// status.  Counts that no region holds (negative, fewer words than records,
+// more words than the region) contribute nothing.
+struct CsCarryPack {
+    const int32_t *lemmas;
+    const int64_t *lemma_begin, *carry;
+    int32_t *kib, *kcb, *klits;
+    int64_t clause_cap, lit_cap;
+    int64_t *totals;
+    int num_instances;
+};
+
+__device__ __forceinline__ void cs_carry_contribution(const CsCarryPack &P, int b, int64_t *n, int64_t *l) {
+    const int64_t r = P.carry[2 * (int64_t)b], wd = P.carry[2 * (int64_t)b + 1];
+    const bool ok = r > 0 && wd >= 2 * r && wd <= P.lemma_begin[b + 1] - P.lemma_begin[b];
+    *n = ok ? r : 0;
+    *l = ok ? wd - r : 0;
+}
+
+// One wavefront, as the packs' scan above.  There is no info word to keep an
+// instance's literal offset in: it goes where its first clause's offset belongs,
+// which the copy kernel reads before it writes the same value there.
+__global__ void __launch_bounds__(64) cdcl_carry_pack_scan_kernel(CsCarryPack P) {
+    const int ln = lane_id(), B = P.num_instances;
+    int64_t sn = 0, sl = 0;
+    for (int b = ln; b < B; b += 64) {
+        int64_t n, l;
+        cs_carry_contribution(P, b, &n, &l);
+        sn += n;
+        sl += l;
+    }
+    const int64_t tn = __shfl(cs_incl_scan64(sn), 63, 64), tl = __shfl(cs_incl_scan64(sl), 63, 64);
+    const bool fits = tn <= P.clause_cap && tl <= P.lit_cap && tn <= INT32_MAX - 1 && tl <= INT32_MAX;
+    if (ln == 0) {
+        P.totals[0] = tn;
+        P.totals[1] = tl;
+        P.kib[B] = fits ? (int32_t)tn : 0;
+    }
+    int64_t cn = 0, cl = 0;
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int b = b0 + ln;
+        int64_t n = 0, l = 0;
+        if (b < B) cs_carry_contribution(P, b, &n, &l);
+        const int64_t in = cs_incl_scan64(n), il = cs_incl_scan64(l);
+        if (b < B) {
+            P.kib[b] = fits ? (int32_t)(cn + in - n) : 0;
+            if (fits && n > 0) P.kcb[cn + in - n] = (int32_t)(cl + il - l);   // (< tn <= clause_cap)
+        }
+        cn += __shfl(in, 63, 64);
+        cl += __shfl(il, 63, 64);
+    }
+    if (ln == 0) P.kcb[fits ? tn : 0] = fits ? (int32_t)tl : 0;   // (after the offsets: with no lemma it is word 0)
+}
+
+// One wavefront per instance, record after record.
+__global__ void __launch_bounds__(256) cdcl_carry_pack_copy_kernel(CsCarryPack P) {
+    const int ln = lane_id();
+    const int waves = (int)(gridDim.x * (blockDim.x >> 6));
+    for (int b = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); b < P.num_instances; b += waves) {
+        const int cb = P.kib[b];
+        const int n = P.kib[b + 1] - cb;
+        if (n <= 0) continue;   // no lemma kept, or totals that do not fit
+        const int64_t words = P.carry[2 * (int64_t)b + 1];   // (within the region: the scan counted it)
+        const int64_t lbase = uniform_i32(P.kcb[cb]);
+        wave_sync();
+        const int32_t *rec = P.lemmas + P.lemma_begin[b];
+        int64_t p = 0;
+        for (int k = 0; k < n && p < words; ++k) {
+            const int len = max(uniform_i32(rec[p]), 0);
+            const int64_t at = lbase + p - k;   // the words before it, less their headers
+            if (ln == 0 && cb + (int64_t)k < P.clause_cap) P.kcb[cb + k] = (int32_t)at;
+            for (int j = ln; j < len && p + 1 + j < words; j += 64)
+                if (at + j < P.lit_cap) P.klits[at + j] = rec[p + 1 + j];
+            p += 1 + (int64_t)len;
+        }
+    }
+}
+
+// The host form's carried records, from their image to the head of each region
+// (one wavefront per instance).  A chain larger than its region stays where it
+// is: the search refuses that instance before it reads a word.
+__global__ void __launch_bounds__(256) cdcl_carry_place_kernel(const int32_t *image, const int64_t *image_begin,
+                                                               int32_t *lemmas, const int64_t *lemma_begin,
+                                                               int num_instances) {
+    const int ln = lane_id();
+    const int waves = (int)(gridDim.x * (blockDim.x >> 6));
+    for (int b = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)); b < num_instances; b += waves) {
+        const int64_t from = image_begin[b], n = image_begin[b + 1] - from, to = lemma_begin[b];
+        if (n > lemma_begin[b + 1] - to) continue;
+        for (int64_t j = ln; j < n; j += 64) lemmas[to + j] = image[from + j];
+    }
+}
+
 // ------------------------------------------------------------------ host side
 namespace {
 
 constexpr OomText CS_OOM{"satmi_cdcl_sound_batch_host", "split the batch"};
 constexpr OomText CS_ASSUME_OOM{"satmi_cdcl_assume_batch_host", "split the batch"};
+constexpr OomText CS_CARRY_OOM{"satmi_cdcl_carry_batch_host", "split the batch"};
 
 std::atomic<int> g_cs_grid{0}, g_cs_wpg{0};      // satmi_cdcl_sound_debug_grid
 std::atomic<int64_t> g_cs_room{0};               // satmi_cdcl_sound_debug_room
@@ -325,6 +448,7 @@ std::atomic<int64_t> g_cs_room{0};               // satmi_cdcl_sound_debug_room
 // the batch, the proof and the outputs, and the lemma regions.
 struct CdclSoundWork : WorkStream {
     DevBuf block, lemmas;
+    PinBuf carry_h;   // satmi_cdcl_carry_batch_host: the carried records, their ranges and counts
 };
 
 int cs_too_large(const char *who, int64_t max_vars) {
@@ -366,8 +490,15 @@ struct CsAssumeIo {
     int core_stride;
 };
 
-// Both device forms: `as` = nullptr is satmi_cdcl_sound_batch_device, its kernels and all.
-int cs_solve_device(const char *who, const CsAssumeIo *as, int num_instances, const int32_t *d_inst_clause_begin,
+// The carried-lemma counts of satmi_cdcl_carry_batch_device.
+struct CsCarryDev {
+    const int64_t *in;
+    int64_t *out;
+};
+
+// The device forms: `as` = nullptr is satmi_cdcl_sound_batch_device, its kernels and all;
+// `cy` (with `as`) is satmi_cdcl_carry_batch_device.
+int cs_solve_device(const char *who, const CsAssumeIo *as, const CsCarryDev *cy, int num_instances, const int32_t *d_inst_clause_begin,
                     const int32_t *d_clause_lit_begin, const int32_t *d_lits, const int32_t *d_inst_nvars,
                     int max_vars, int max_clause_len, int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
                     const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters, int32_t *d_row_len,
@@ -382,6 +513,7 @@ int cs_solve_device(const char *who, const CsAssumeIo *as, int num_instances, co
         return fail_arg(who, "null pointer");
     if (as && (!as->begin || !as->lits || !as->core_len || (as->core_stride > 0 && !as->core_lits)))
         return fail_arg(who, "null pointer");
+    if (cy && !cy->out) return fail_arg(who, "null pointer");
     if (max_vars > SATMI_CDCL_SOUND_MAX_VARS) return cs_too_large(who, max_vars);
     DeviceFacts facts;
     SATMI_TRY(device_facts(&facts));
@@ -423,6 +555,25 @@ int cs_solve_device(const char *who, const CsAssumeIo *as, int num_instances, co
     const int grid = batch_grid(facts, lds_bytes, 0, 64 * wpg, wgs, g_cs_grid);
     const bool long_form = max_clause_len <= 0 || max_clause_len > CS_SHORT_MAX;
     hipStream_t s = (hipStream_t)stream;
+    if (cy) {
+        CsCarryArgs CA{};
+        static_cast<CsArgs &>(CA) = A;
+        CA.assume_begin = as->begin;
+        CA.assume_lits = as->lits;
+        CA.core_len = as->core_len;
+        CA.core_lits = as->core_lits;
+        CA.core_stride = as->core_stride;
+        CA.carry_in = cy->in;
+        CA.carry_out = cy->out;
+        const void *fn = long_form ? (const void *)cdcl_carry_kernel<true> : (const void *)cdcl_carry_kernel<false>;
+        SATMI_TRY(batch_allow_lds(fn, lds_bytes));
+        if (long_form)
+            hipLaunchKernelGGL(cdcl_carry_kernel<true>, dim3(grid), dim3(64 * wpg), lds_bytes, s, CA);
+        else
+            hipLaunchKernelGGL(cdcl_carry_kernel<false>, dim3(grid), dim3(64 * wpg), lds_bytes, s, CA);
+        SATMI_HIP(hipGetLastError());
+        return SATMI_OK;
+    }
     if (as) {
         CsAssumeArgs AA{};
         static_cast<CsArgs &>(AA) = A;
@@ -494,7 +645,7 @@ extern "C" int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d
                                              const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
                                              int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
                                              void *stream) {
-    return cs_solve_device("satmi_cdcl_sound_batch_device", nullptr, num_instances, d_inst_clause_begin,
+    return cs_solve_device("satmi_cdcl_sound_batch_device", nullptr, nullptr, num_instances, d_inst_clause_begin,
                            d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
                            time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
                            d_info, stream);
@@ -510,10 +661,59 @@ extern "C" int satmi_cdcl_assume_batch_device(int num_instances, const int32_t *
                                               int32_t *d_core_len, int32_t *d_core_lits, int core_stride,
                                               void *stream) {
     const CsAssumeIo as{d_assume_begin, d_assume_lits, d_core_len, d_core_lits, core_stride};
-    return cs_solve_device("satmi_cdcl_assume_batch_device", &as, num_instances, d_inst_clause_begin,
+    return cs_solve_device("satmi_cdcl_assume_batch_device", &as, nullptr, num_instances, d_inst_clause_begin,
                            d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
                            time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
                            d_info, stream);
+}
+
+extern "C" int satmi_cdcl_carry_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                             const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                             const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                             int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                             const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                             int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                             const int32_t *d_assume_begin, const int32_t *d_assume_lits,
+                                             int32_t *d_core_len, int32_t *d_core_lits, int core_stride,
+                                             const int64_t *d_carry_in, int64_t *d_carry_out, void *stream) {
+    const CsAssumeIo as{d_assume_begin, d_assume_lits, d_core_len, d_core_lits, core_stride};
+    const CsCarryDev cy{d_carry_in, d_carry_out};
+    return cs_solve_device("satmi_cdcl_carry_batch_device", &as, &cy, num_instances, d_inst_clause_begin,
+                           d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
+                           time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
+                           d_info, stream);
+}
+
+extern "C" int satmi_cdcl_carry_pack_device(int num_instances, const int32_t *d_lemmas, const int64_t *d_lemma_begin,
+                                            const int64_t *d_carry, int32_t *d_kept_inst_begin,
+                                            int32_t *d_kept_clause_begin, int64_t kept_clause_cap,
+                                            int32_t *d_kept_lits, int64_t kept_lit_cap, int64_t *d_totals,
+                                            void *stream) {
+    const char *who = "satmi_cdcl_carry_pack_device";
+    if (num_instances < 0) return fail_arg(who, "negative formula count");
+    if (kept_clause_cap < 0 || kept_lit_cap < 0) return fail_arg(who, "negative kept capacity");
+    if (num_instances == 0) return SATMI_OK;
+    if (!d_lemmas || !d_lemma_begin || !d_carry || !d_kept_inst_begin || !d_kept_clause_begin || !d_kept_lits ||
+        !d_totals)
+        return fail_arg(who, "null pointer");
+    CsCarryPack P{};
+    P.lemmas = d_lemmas;
+    P.lemma_begin = d_lemma_begin;
+    P.carry = d_carry;
+    P.kib = d_kept_inst_begin;
+    P.kcb = d_kept_clause_begin;
+    P.klits = d_kept_lits;
+    P.clause_cap = kept_clause_cap;
+    P.lit_cap = kept_lit_cap;
+    P.totals = d_totals;
+    P.num_instances = num_instances;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(cdcl_carry_pack_scan_kernel, dim3(1), dim3(64), 0, s, P);
+    SATMI_HIP(hipGetLastError());
+    const int wgs = std::min((num_instances + 3) / 4, 8192);
+    hipLaunchKernelGGL(cdcl_carry_pack_copy_kernel, dim3(wgs), dim3(256), 0, s, P);
+    SATMI_HIP(hipGetLastError());
+    return SATMI_OK;
 }
 
 extern "C" int satmi_cdcl_sound_pack_device(int num_instances, const int32_t *d_status, const int32_t *d_lemmas,
@@ -538,8 +738,18 @@ extern "C" int satmi_cdcl_assume_pack_device(int num_instances, const int32_t *d
 
 namespace {
 
-// Both host forms: `as` = nullptr is satmi_cdcl_sound_batch_host, else its host arrays.
-int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int num_instances,
+// The carried lemmas and the kept output of satmi_cdcl_carry_batch_host, both clause triples.
+struct CsCarryIo {
+    const int32_t *cib, *ccb, *clits;
+    int32_t *kib, *kcb;
+    int64_t kclause_cap;
+    int32_t *klits;
+    int64_t klit_cap;
+};
+
+// The host forms: `as` = nullptr is satmi_cdcl_sound_batch_host, else its host arrays;
+// `cy` (with `as`) is satmi_cdcl_carry_batch_host, whose h_totals has four words.
+int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, const CsCarryIo *cy, int num_instances,
                   const int32_t *h_inst_clause_begin, const int32_t *h_clause_lit_begin, const int32_t *h_lits,
                   const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s, int64_t room_cap,
                   int32_t *h_status, int64_t *h_counters, int32_t *h_row_len, int32_t *h_row_lits, int stride,
@@ -552,10 +762,14 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
                       : room_cap < 0                            ? "negative room_cap"
                       : stride < 1                              ? "row stride < 1"
                       : as && as->core_stride < 0               ? "negative core_stride"
+                      : cy && (cy->kclause_cap < 0 || cy->klit_cap < 0) ? "negative kept capacity"
                                                                 : nullptr;
+    // (the kept arrays: all three, or none of them and no capacity)
+    const bool kept = cy && (cy->kib || cy->kcb || cy->klits || cy->kclause_cap > 0 || cy->klit_cap > 0);
     const bool outs = h_inst_nvars && h_status && h_counters && h_row_len && h_row_lits && h_proof_inst_begin &&
                       h_proof_clause_begin && h_proof_lits && h_totals &&
-                      (!as || (as->begin && as->core_len && (as->core_stride == 0 || as->core_lits)));
+                      (!as || (as->begin && as->core_len && (as->core_stride == 0 || as->core_lits))) &&
+                      (!kept || (cy->kib && cy->kcb && cy->klits));
     if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits, own, outs,
                                           &sh, nv.data()))
         return fail_arg(who, bad);
@@ -583,6 +797,13 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
                 if (x == 0 || x == INT32_MIN) return fail_arg(who, "assumption literal 0 / INT32_MIN");
                 if (std::abs(x) > h_inst_nvars[b]) return fail_arg(who, "assumption literal beyond inst_nvars");
             }
+    }
+    int64_t image_words = 0;
+    if (cy) {
+        if (cy->kclause_cap > INT32_MAX - 1 || cy->klit_cap > INT32_MAX)
+            return fail_arg(who, "kept capacity beyond the 32-bit offsets of the kept arrays");
+        if (const char *bad = carry_triple_check(num_instances, cy->cib, cy->ccb, cy->clits, h_inst_nvars, &image_words))
+            return fail_arg(who, bad);
     }
     if (max_vars > SATMI_CDCL_SOUND_MAX_VARS) return cs_too_large(who, max_vars);
 
@@ -619,6 +840,15 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
     const size_t o_al = as ? cv.take(4 * (size_t)std::max(Atot, 1)) : 0;
     const size_t o_cl = as ? cv.take(4 * B) : 0;
     const size_t o_core = as ? cv.take(4 * std::max<size_t>(B * cstride, 1)) : 0;
+    const size_t kccap = cy ? (size_t)cy->kclause_cap : 0, klcap = cy ? (size_t)cy->klit_cap : 0;
+    const size_t o_cin = cy ? cv.take(16 * B) : 0;        // the carried counts, read by every run
+    const size_t o_cout = cy ? cv.take(16 * B) : 0;       // the kept counts of the last run
+    const size_t o_cbeg = cy ? cv.take(8 * (B + 1)) : 0;
+    const size_t o_cimg = cy ? cv.take(4 * (size_t)std::max<int64_t>(image_words, 1)) : 0;
+    const size_t o_ktot = cy ? cv.take(16) : 0;
+    const size_t o_kib = cy ? cv.take(4 * (B + 1)) : 0;
+    const size_t o_kcb = cy ? cv.take(4 * (kccap + 1)) : 0;
+    const size_t o_klits = cy ? cv.take(4 * std::max<size_t>(klcap, 1)) : 0;
     SATMI_TRY(wk.block.reserve(cv.at, oom));
     const Staged d{wk.block.as<unsigned char>(), s};
     SATMI_TRY(d.up(o_icb, h_inst_clause_begin, 4 * (B + 1)));
@@ -635,12 +865,29 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
                          d.at<int32_t>(o_core), as->core_stride};
     }
 
+    // ---- the carried records, laid out in pinned memory: one upload each of image, ranges and counts
+    std::vector<int64_t> carried(B, 0);   // words per instance
+    CsCarryDev dcy{};
+    if (cy) {
+        const size_t img = 4 * (size_t)image_words, beg = 8 * (B + 1), cnt = 16 * B;
+        const size_t at_beg = (img + 7) & ~(size_t)7, at_cnt = at_beg + beg;
+        SATMI_TRY(wk.carry_h.reserve(at_cnt + cnt));
+        int64_t *hb = (int64_t *)(wk.carry_h.p + at_beg), *hc = (int64_t *)(wk.carry_h.p + at_cnt);
+        carry_records_layout(num_instances, cy->cib, cy->ccb, cy->clits, hb, (int32_t *)wk.carry_h.p, hc);
+        for (size_t b = 0; b < B; ++b) carried[b] = hc[2 * b + 1];
+        SATMI_TRY(d.up(o_cimg, wk.carry_h.p, img));
+        SATMI_TRY(d.up(o_cbeg, hb, beg));
+        SATMI_TRY(d.up(o_cin, hc, cnt));
+        dcy = CsCarryDev{d.at<const int64_t>(o_cin), d.at<int64_t>(o_cout)};
+    }
+
     // ---- solve; again with four times the room for the instances that ended FULL, up to the caller's cap
     const int64_t dbg_room = g_cs_room.load();
     const int64_t cap = room_cap > 0 ? room_cap : (int64_t)INT32_MAX - sh.max_clauses - 1;
     const int64_t first = dbg_room > 0 ? dbg_room
                                        : std::min<int64_t>(65536, std::max<int64_t>(256, ((int64_t)16 << 20) / (int64_t)B));
     std::vector<int64_t> room(B, std::min(first, cap));
+    for (size_t b = 0; b < B; ++b) room[b] = std::min(carried[b] + first, cap);   // (the carried words, then the usual room)
     std::vector<int64_t> lb(B + 1), info(B * SATMI_CDCL_SOUND_NWORDS);
     std::vector<int32_t> status(B);
     for (int round = 0; round < 32; ++round) {
@@ -648,9 +895,17 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
         for (size_t b = 0; b < B; ++b) lb[b + 1] = lb[b] + room[b];
         SATMI_TRY(wk.lemmas.reserve(4 * (size_t)std::max<int64_t>(lb[B], 1), oom));
         SATMI_TRY(d.up(o_lb, lb.data(), 8 * (B + 1)));
+        if (cy && image_words > 0) {   // every run starts from the input carry
+            hipLaunchKernelGGL(cdcl_carry_place_kernel, dim3(std::min((num_instances + 3) / 4, 8192)), dim3(256), 0, s,
+                               d.at<const int32_t>(o_cimg), d.at<const int64_t>(o_cbeg), wk.lemmas.as<int32_t>(),
+                               d.at<const int64_t>(o_lb), num_instances);
+            SATMI_HIP(hipGetLastError());
+        }
         SATMI_TRY(cs_solve_device(
-            as ? "satmi_cdcl_assume_batch_device" : "satmi_cdcl_sound_batch_device", as ? &das : nullptr,
-            num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
+            cy   ? "satmi_cdcl_carry_batch_device"
+            : as ? "satmi_cdcl_assume_batch_device"
+                 : "satmi_cdcl_sound_batch_device",
+            as ? &das : nullptr, cy ? &dcy : nullptr, num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
             d.at<const int32_t>(o_nv), max_vars, C > 0 ? sh.max_len : 0, conflict_limit, time_limit_s,
             wk.lemmas.as<int32_t>(), d.at<const int64_t>(o_lb), d.at<int32_t>(o_st), d.at<int64_t>(o_ctr),
             d.at<int32_t>(o_rl), d.at<int32_t>(o_row), stride, d.at<int64_t>(o_info), s));
@@ -669,8 +924,16 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
                              d.at<const int64_t>(o_lb), d.at<int64_t>(o_info), d.at<int32_t>(o_pib),
                              d.at<int32_t>(o_pcb), proof_clause_cap, d.at<int32_t>(o_plits), proof_lit_cap,
                              d.at<int64_t>(o_tot), s));
+    int64_t totals[4] = {0, 0, 0, 0};
+    if (cy) {
+        SATMI_TRY(satmi_cdcl_carry_pack_device(num_instances, wk.lemmas.as<const int32_t>(), d.at<const int64_t>(o_lb),
+                                               d.at<const int64_t>(o_cout), d.at<int32_t>(o_kib), d.at<int32_t>(o_kcb),
+                                               cy->kclause_cap, d.at<int32_t>(o_klits), cy->klit_cap,
+                                               d.at<int64_t>(o_ktot), s));
+        SATMI_TRY(d.down(totals + 2, o_ktot, 16));
+        if (kept) SATMI_TRY(d.down(cy->kib, o_kib, 4 * (B + 1)));
+    }
     // ---- copy back
-    int64_t totals[2] = {0, 0};
     SATMI_TRY(d.down(totals, o_tot, 16));
     SATMI_TRY(d.down(info.data(), o_info, 8 * B * SATMI_CDCL_SOUND_NWORDS));
     SATMI_TRY(d.down(h_counters, o_ctr, 8 * B * SATMI_CDCL_SOUND_NCOUNTERS));
@@ -687,11 +950,17 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, int
     // (totals that do not fit: no instance has a lemma, and proof_clause_begin is its first word)
     SATMI_TRY(d.down(h_proof_clause_begin, o_pcb, 4 * (size_t)((fits ? totals[0] : 0) + 1)));
     SATMI_TRY(d.down(h_proof_lits, o_plits, fits ? 4 * (size_t)totals[1] : 0));
+    if (kept) {
+        const bool kfits = totals[2] <= cy->kclause_cap && totals[3] <= cy->klit_cap;
+        SATMI_TRY(d.down(cy->kcb, o_kcb, 4 * (size_t)((kfits ? totals[2] : 0) + 1)));
+        SATMI_TRY(d.down(cy->klits, o_klits, kfits ? 4 * (size_t)totals[3] : 0));
+    }
     SATMI_HIP(hipStreamSynchronize(s));
     std::memcpy(h_status, status.data(), 4 * B);
     if (h_info) std::memcpy(h_info, info.data(), 8 * B * SATMI_CDCL_SOUND_NWORDS);
     h_totals[0] = totals[0];
     h_totals[1] = totals[1];
+    if (cy) h_totals[2] = totals[2], h_totals[3] = totals[3];
     if (wk.lemmas.cap > ((size_t)256 << 20)) wk.lemmas.release();   // large regions are not kept in the pool
     return SATMI_OK;
 }
@@ -706,7 +975,7 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
                                            int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
                                            int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
                                            int64_t *h_info, int64_t *h_totals) {
-    return cs_batch_host("satmi_cdcl_sound_batch_host", &CS_OOM, nullptr, num_instances, h_inst_clause_begin,
+    return cs_batch_host("satmi_cdcl_sound_batch_host", &CS_OOM, nullptr, nullptr, num_instances, h_inst_clause_begin,
                          h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
                          h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
                          proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
@@ -723,7 +992,29 @@ extern "C" int satmi_cdcl_assume_batch_host(int num_instances, const int32_t *h_
                                             const int32_t *h_assume_lits, int32_t *h_core_len, int32_t *h_core_lits,
                                             int core_stride) {
     const CsAssumeIo as{h_assume_begin, h_assume_lits, h_core_len, h_core_lits, core_stride};
-    return cs_batch_host("satmi_cdcl_assume_batch_host", &CS_ASSUME_OOM, &as, num_instances, h_inst_clause_begin,
+    return cs_batch_host("satmi_cdcl_assume_batch_host", &CS_ASSUME_OOM, &as, nullptr, num_instances, h_inst_clause_begin,
+                         h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
+                         h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
+                         proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
+}
+
+extern "C" int satmi_cdcl_carry_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                           const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                           const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                           int64_t room_cap, int32_t *h_status, int64_t *h_counters,
+                                           int32_t *h_row_len, int32_t *h_row_lits, int stride,
+                                           int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
+                                           int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
+                                           int64_t *h_info, int64_t *h_totals, const int32_t *h_assume_begin,
+                                           const int32_t *h_assume_lits, int32_t *h_core_len, int32_t *h_core_lits,
+                                           int core_stride, const int32_t *h_carry_inst_begin,
+                                           const int32_t *h_carry_clause_begin, const int32_t *h_carry_lits,
+                                           int32_t *h_kept_inst_begin, int32_t *h_kept_clause_begin,
+                                           int64_t kept_clause_cap, int32_t *h_kept_lits, int64_t kept_lit_cap) {
+    const CsAssumeIo as{h_assume_begin, h_assume_lits, h_core_len, h_core_lits, core_stride};
+    const CsCarryIo cy{h_carry_inst_begin, h_carry_clause_begin, h_carry_lits, h_kept_inst_begin,
+                       h_kept_clause_begin, kept_clause_cap, h_kept_lits, kept_lit_cap};
+    return cs_batch_host("satmi_cdcl_carry_batch_host", &CS_CARRY_OOM, &as, &cy, num_instances, h_inst_clause_begin,
                          h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
                          h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
                          proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);

@@ -1,7 +1,11 @@
 // cdcl_sound_search.inc -- the two kernels of cdcl_sound.hip that have an
 // assumption-carrying form: the search and the pack's scan.  cdcl_sound.hip
-// includes this text twice, with
+// includes this text three times, with
 //   CS_ASSUME            0: satmi_cdcl_sound_*'s kernels; 1: satmi_cdcl_assume_*'s
+//   CS_CARRY             1 (with CS_ASSUME 1): satmi_cdcl_carry_batch_device's search
+//                        kernel, whose instances start with carried lemmas in their
+//                        regions (CsCarryArgs); it has a pack of its own, so the
+//                        third inclusion defines no scan kernel
 //   CS_SEARCH_KERNEL     the search kernel's name, CS_SEARCH_ARGS its argument struct
 //   CS_PACK_SCAN_KERNEL  the pack scan kernel's name
 // Kernel bodies, not functions inlined into two wrappers: with CS_ASSUME 0 the
@@ -10,7 +14,7 @@
 // (tools/isa_compare.py).  The lines of the other form are under #if CS_ASSUME:
 // the instance carries an ordered list of assumption literals (CsAssumeArgs),
 // read from the caller's arrays where they lie; level i <= k belongs to
-// assumption i.
+// assumption i.  The lines of the carrying form are under #if CS_CARRY.
 template <bool LONG>
 __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t cs_lds[];
@@ -64,6 +68,15 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
             if (__ballot(bad) != 0ull) status = SATMI_CDCL_SOUND_TOO_LARGE;
         }
 #endif
+#if CS_CARRY
+        // ---- the carried lemmas: carry_in[b] = (records, words) that lie in the region already
+        int64_t cin_r = 0, cin_w = 0;
+        bool bad_carry = false;
+        if (A.carry_in) {
+            cin_r = A.carry_in[2 * b];
+            cin_w = A.carry_in[2 * b + 1];
+        }
+#endif
         if (status == CS_RUNNING) {
             for (int v = ln; v <= w.nv; v += 64) {
                 w.reason[v] = CS_NONE;
@@ -79,6 +92,38 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
 #endif
             wave_sync();
         }
+#if CS_CARRY
+        if (status == CS_RUNNING) {
+            // The chain must hold `cin_r` records of at least one literal each, over the
+            // instance's variables, and end on word `cin_w` exactly; codes m + offset stay
+            // below 2^31.  One header per step, the lanes over its literals, which occur.
+            bad_carry = cin_r < 0 || cin_w < 0 || cin_w > w.room || (int64_t)w.m + cin_w > (int64_t)INT32_MAX;
+            int64_t p = 0, k = 0;
+            bool lbad = false;
+            for (; !bad_carry && k < cin_r && p < cin_w; ++k) {
+                const int len = uniform_i32(w.rec[p]);
+                if (len < 1 || (int64_t)len > cin_w - p - 1) {
+                    bad_carry = true;
+                    break;
+                }
+                for (int j = ln; j < len; j += 64) {
+                    const uint32_t v = cs_var(w.rec[p + 1 + j]);
+                    if (v - 1u >= (uint32_t)w.nv) lbad = true;
+                    else w.flags[v] = 8u;
+                }
+                p += 1 + (int64_t)len;
+            }
+            bad_carry = bad_carry || k != cin_r || p != cin_w || __ballot(lbad) != 0ull;
+            wave_sync();
+            if (bad_carry) {
+                status = SATMI_CDCL_SOUND_TOO_LARGE;
+            } else {
+                w.used = cin_w;
+                records = cin_r;
+                words = cin_w;
+            }
+        }
+#endif
         // Every pass of the loop ends the instance, learns a clause (two words of
         // the region at least) or decides (at most nv decisions between conflicts).
 #if CS_ASSUME   // (or opens an assumption's level: at most na between conflicts)
@@ -385,6 +430,14 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
 #if CS_ASSUME
             A.core_len[b] = status == SATMI_CDCL_SOUND_ASSUMED ? core : 0;
 #endif
+#if CS_CARRY
+            // the non-empty records in the region: the carried ones and those learned and
+            // written, without the closing record; a refused instance's input, or none of a bad carry
+            const bool ran = status != SATMI_CDCL_SOUND_TOO_LARGE;
+            const bool closed = status == SATMI_CDCL_SOUND_UNSAT || status == SATMI_CDCL_SOUND_ASSUMED;
+            A.carry_out[2 * b] = bad_carry ? 0 : ran ? cin_r + learned : cin_r;
+            A.carry_out[2 * b + 1] = bad_carry ? 0 : ran ? w.used - (closed ? 1 : 0) : cin_w;
+#endif
         }
         if (ln < SATMI_CDCL_SOUND_NCOUNTERS)
             A.counters[b * SATMI_CDCL_SOUND_NCOUNTERS + ln] = ln == 0   ? conflicts
@@ -398,12 +451,18 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
         if (ln < SATMI_CDCL_SOUND_NWORDS)
             A.info[b * SATMI_CDCL_SOUND_NWORDS + ln] = ln == 0   ? records
                                                        : ln == 1 ? words
+#if CS_CARRY
+                                                       : ln == 2 ? (trunc ? SATMI_CDCL_SOUND_TRUNCATED : 0) |
+                                                                       (bad_carry ? SATMI_CDCL_SOUND_BAD_CARRY : 0)
+#else
                                                        : ln == 2 ? (trunc ? SATMI_CDCL_SOUND_TRUNCATED : 0)
+#endif
                                                                  : 0;
         wave_sync();
     }
 }
 
+#if !CS_CARRY
 // One wavefront: the totals, whether they fit, and the offsets by an exclusive
 // scan, 64 instances at a time.  Totals that do not fit leave every instance
 // with no lemma, as dpll_proof.hip's pack does.
@@ -439,3 +498,4 @@ __global__ void __launch_bounds__(64) CS_PACK_SCAN_KERNEL(CsPack P) {
         cl += __shfl(il, 63, 64);
     }
 }
+#endif

@@ -61,6 +61,7 @@ CDCL_SOUND_COUNTERS = ("conflicts", "decisions", "propagated", "rounds", "learne
 CDCL_SOUND_NWORDS = 4
 CDCL_SOUND_WORDS = ("records", "region_words", "flags", "first_literal")
 CDCL_SOUND_TRUNCATED = 1
+CDCL_SOUND_BAD_CARRY = 2   # satmi_cdcl_carry_*: the carried records were malformed
 CDCL_SOUND_MAX_VARS = 8191
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
@@ -85,6 +86,7 @@ EXPORTED = (
     "satmi_cdcl_sound_batch_device", "satmi_cdcl_sound_pack_device", "satmi_cdcl_sound_batch_host",
     "satmi_cdcl_sound_debug_grid", "satmi_cdcl_sound_debug_room", "satmi_cdcl_sound_lds_bytes",
     "satmi_cdcl_assume_batch_device", "satmi_cdcl_assume_pack_device", "satmi_cdcl_assume_batch_host",
+    "satmi_cdcl_carry_batch_device", "satmi_cdcl_carry_pack_device", "satmi_cdcl_carry_batch_host",
 )
 
 
@@ -250,6 +252,14 @@ def load():
         [ctypes.c_int] + [i32p] * 4 + [ctypes.c_int64, ctypes.c_double, ctypes.c_int64]
         + [i32p, i64p, i32p, i32p, ctypes.c_int] + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64, i64p, i64p]
         + [i32p] * 4 + [ctypes.c_int])
+    L.satmi_cdcl_carry_batch_device.argtypes = (
+        [ctypes.c_int] + [vp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_double] + [vp] * 6
+        + [ctypes.c_int, vp] + [vp] * 4 + [ctypes.c_int, vp, vp, vp])
+    L.satmi_cdcl_carry_pack_device.argtypes = [ctypes.c_int] + [vp] * 5 + [ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
+    L.satmi_cdcl_carry_batch_host.argtypes = (
+        [ctypes.c_int] + [i32p] * 4 + [ctypes.c_int64, ctypes.c_double, ctypes.c_int64]
+        + [i32p, i64p, i32p, i32p, ctypes.c_int] + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64, i64p, i64p]
+        + [i32p] * 4 + [ctypes.c_int] + [i32p] * 3 + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64])
     L.satmi_cdcl_sound_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     L.satmi_cdcl_sound_debug_room.argtypes = [ctypes.c_int64]
     L.satmi_cdcl_sound_lds_bytes.restype = ctypes.c_uint64

@@ -227,3 +227,137 @@ def pack_device(num_instances, status, lemmas, lemma_begin, info, proof_icb, pro
         int(num_instances), status, lemmas, lemma_begin, info, proof_icb, proof_clb, int(proof_clause_cap),
         proof_lits, int(proof_lit_cap), totals, stream)
     _capi.check(rc, "satmi_cdcl_sound_pack_device")
+
+
+# ---- with carried lemmas (satmi_cdcl_carry_*): one query after another on the same formula
+def pack_carry(carry, num_instances):
+    """Per-formula lists of carried clauses -> the carry triple (inst_begin int32 [B + 1],
+    clause_begin int32, lits int32, never empty).  None = nothing carried anywhere."""
+    lists = [[] for _ in range(num_instances)] if carry is None else [[list(c) for c in cl] for cl in carry]
+    if len(lists) != num_instances:
+        raise ValueError("carry must have one list of clauses per formula")
+    flat = [int(l) for cl in lists for c in cl for l in c]
+    if any(not -2 ** 31 < l < 2 ** 31 for l in flat):
+        raise ValueError("carried literals must be within int32 (INT32_MIN excluded)")
+    cib = np.zeros(num_instances + 1, dtype=np.int32)
+    np.cumsum([len(cl) for cl in lists], out=cib[1:])
+    ccb = np.zeros(int(cib[-1]) + 1, dtype=np.int32)
+    np.cumsum([len(c) for cl in lists for c in cl], out=ccb[1:])
+    top = np.array([max([abs(int(l)) for c in cl for l in c] + [0]) for cl in lists], dtype=np.int32)
+    return cib, ccb, np.array(flat or [0], dtype=np.int32), top
+
+
+def cdcl_carry_packed(batch, assume_begin, assume_lits, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0,
+                      room=None, core_stride=None, kept_room=None):
+    """satmi_cdcl_carry_batch_host on a CnfBatch whose inst_nvars cover the variables of the
+    assumptions and of the carried clauses; `carry` = the triple (inst_begin, clause_begin,
+    lits) of pack_carry, or None.  Returns cdcl_assume_packed's eight and the kept lemmas as a
+    CnfBatch: "formula" b of it is what the next query on formula b carries, whatever this
+    one's status.  `kept_room` = (lemmas, literals) the first call's kept arrays hold; like the
+    proof's, kept arrays that are outgrown are asked for again with 4x the room."""
+    L = _capi.load()
+    _capi.require_gpu()
+    B = batch.num_instances
+    assume_begin = np.ascontiguousarray(assume_begin, dtype=np.int32)
+    assume_lits = np.ascontiguousarray(assume_lits, dtype=np.int32)
+    cib, ccb, clits = (None, None, None) if carry is None else \
+        (np.ascontiguousarray(a, dtype=np.int32) for a in carry)
+    stride = max(1, int(batch.inst_nvars.max(initial=0)))
+    if core_stride is None:
+        core_stride = max(1, int(np.diff(assume_begin).max(initial=0)))
+    status = np.zeros(B, dtype=np.int32)
+    counters = np.zeros((B, _capi.CDCL_SOUND_NCOUNTERS), dtype=np.int64)
+    row_len = np.zeros(B, dtype=np.int32)
+    row_lits = np.zeros((B, stride), dtype=np.int32)
+    core_len = np.zeros(B, dtype=np.int32)
+    core_lits = np.zeros((B, max(core_stride, 1)), dtype=np.int32)
+    info = np.zeros((B, _capi.CDCL_SOUND_NWORDS), dtype=np.int64)
+    totals = np.zeros(4, dtype=np.int64)
+    pib = np.zeros(B + 1, dtype=np.int32)
+    kib = np.zeros(B + 1, dtype=np.int32)
+    ccap, lcap = room if room is not None else (max(1024, 64 * B), max(16384, 1024 * B))
+    carried = (0, 0) if carry is None else (int(cib[-1] - cib[0]), int(ccb[cib[-1]] - ccb[cib[0]]))
+    kccap, klcap = kept_room if kept_room is not None else (ccap + carried[0], lcap + carried[1])
+    i64 = ctypes.c_int64
+    while True:
+        pcb = np.zeros(ccap + 1, dtype=np.int32)
+        plits = np.zeros(lcap, dtype=np.int32)
+        kcb = np.zeros(kccap + 1, dtype=np.int32)
+        klits = np.zeros(max(klcap, 1), dtype=np.int32)
+        rc = L.satmi_cdcl_carry_batch_host(
+            B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits), _p(batch.inst_nvars),
+            int(conflict_limit), float(time_limit), int(room_cap), _p(status), _p(counters, i64), _p(row_len),
+            _p(row_lits), int(stride), _p(pib), _p(pcb), int(ccap), _p(plits), int(lcap), _p(info, i64),
+            _p(totals, i64), _p(assume_begin), _p(assume_lits), _p(core_len), _p(core_lits), int(core_stride),
+            None if cib is None else _p(cib), None if ccb is None else _p(ccb), None if clits is None else _p(clits),
+            _p(kib), _p(kcb), int(kccap), _p(klits), int(klcap))
+        _capi.check(rc, "satmi_cdcl_carry_batch_host")
+        if B == 0 or (int(totals[0]) <= ccap and int(totals[1]) <= lcap and
+                      int(totals[2]) <= kccap and int(totals[3]) <= klcap):
+            break
+        if int(totals[0]) > ccap or int(totals[1]) > lcap:
+            ccap, lcap = max(4 * ccap, int(totals[0])), max(4 * lcap, int(totals[1]))
+        if int(totals[2]) > kccap or int(totals[3]) > klcap:
+            kccap, klcap = max(4 * kccap, int(totals[2])), max(4 * klcap, int(totals[3]))
+    P = int(pib[B]) if B else 0
+    K = int(kib[B]) if B else 0
+    zeros = np.zeros(B, dtype=np.int32)
+    proof = CnfBatch(pib, pcb[:P + 1].copy(), plits[:max(int(pcb[P]), 1)].copy(), zeros)
+    kept = CnfBatch(kib, kcb[:K + 1].copy(), klits[:max(int(kcb[K]), 1)].copy(), zeros)
+    return status, counters, row_len, row_lits, proof, info, core_len, core_lits[:, :core_stride], kept
+
+
+def cdcl_carry_batch(formulas, assumptions, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0, room=None,
+                     core_stride=None, kept_room=None):
+    """Sound CDCL on `formulas` under `assumptions`, formula b starting with the clauses
+    `carry[b]` as learned clauses (None = nothing carried anywhere): lemmas an earlier query
+    on the same formula, or on a subset of its clauses, kept.  cdcl_assume_batch's dict per
+    formula (with "flags", the info flags) plus "kept", the list of clauses to carry into the
+    next query: the carried ones and those this query learned, whatever its status.  With
+    "sat" False, "proof" holds the carried lemmas too: they are part of the refutation, and
+    that they follow from the formula is the caller's claim, which check_refutations tests."""
+    batch = formulas if isinstance(formulas, CnfBatch) else pack(formulas)
+    B = batch.num_instances
+    begin, lits, top = pack_assumptions(assumptions, B)
+    cib, ccb, clits, ctop = pack_carry(carry, B)
+    batch = CnfBatch(batch.inst_clause_begin, batch.clause_lit_begin, batch.lits,
+                     np.maximum(np.maximum(np.asarray(batch.inst_nvars, dtype=np.int32), top), ctop))
+    status, counters, row_len, row_lits, proof, info, core_len, core_lits, kept = cdcl_carry_packed(
+        batch, begin, lits, None if carry is None else (cib, ccb, clits), conflict_limit, time_limit, room_cap, room,
+        core_stride, kept_room)
+    out = []
+    for b in range(B):
+        st = int(status[b])
+        sat = True if st == _capi.CDCL_SOUND_SAT else \
+            False if st in (_capi.CDCL_SOUND_UNSAT, _capi.CDCL_SOUND_ASSUMED) else None
+        out.append({"status": st, "sat": sat,
+                    "counters": dict(zip(_capi.CDCL_SOUND_COUNTERS, map(int, counters[b]))),
+                    "model": row_lits[b, :int(row_len[b])].tolist() if sat else None,
+                    "proof": [list(c) for c in proof.instance(b)] if sat is False else None,
+                    "core": core_lits[b, :int(core_len[b])].tolist() if sat is False else None,
+                    "core_len": int(core_len[b]),
+                    "records": int(info[b, 0]), "region_words": int(info[b, 1]), "flags": int(info[b, 2]),
+                    "kept": [list(c) for c in kept.instance(b)]})
+    return out
+
+
+def cdcl_carry_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clause_len, lemmas, lemma_begin,
+                      status, counters, row_len, row_lits, stride, info, assume_begin, assume_lits, core_len,
+                      core_lits, core_stride, carry_in, carry_out, conflict_limit=0, time_limit=0.0, stream=None):
+    """satmi_cdcl_carry_batch_device on device pointers (ints, e.g. a tensor's data_ptr();
+    `carry_in` may be None, or the same array as `carry_out`); asynchronous on `stream`."""
+    rc = _capi.load().satmi_cdcl_carry_batch_device(
+        int(num_instances), icb, clb, lits, inst_nvars, int(max_vars), int(max_clause_len), int(conflict_limit),
+        float(time_limit), lemmas, lemma_begin, status, counters, row_len, row_lits, int(stride), info,
+        assume_begin, assume_lits, core_len, core_lits, int(core_stride), carry_in, carry_out, stream)
+    _capi.check(rc, "satmi_cdcl_carry_batch_device")
+
+
+def carry_pack_device(num_instances, lemmas, lemma_begin, carry, kept_icb, kept_clb, kept_clause_cap, kept_lits,
+                      kept_lit_cap, totals, stream=None):
+    """satmi_cdcl_carry_pack_device: every formula's kept lemmas (its first carry[b] records) as
+    a clause triple, on the same stream as the solve."""
+    rc = _capi.load().satmi_cdcl_carry_pack_device(
+        int(num_instances), lemmas, lemma_begin, carry, kept_icb, kept_clb, int(kept_clause_cap), kept_lits,
+        int(kept_lit_cap), totals, stream)
+    _capi.check(rc, "satmi_cdcl_carry_pack_device")

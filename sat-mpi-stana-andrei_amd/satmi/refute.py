@@ -73,6 +73,11 @@ def check_refutations(formulas_or_batch, proofs, lemmas=False):
     return res
 
 
+def check_refutation(formula, proof):
+    """check_refutations on one formula: whether `proof` refutes it."""
+    return check_refutations([formula], [proof])[0]["proven"]
+
+
 def check_refutations_device(num_instances, icb, clb, lits, proof_icb, proof_clb, proof_lits, max_vars,
                              max_clause_len, out, lemma_ok=None, stream=None):
     """satmi_check_refutations_device on device pointers (ints, e.g. a tensor's data_ptr();

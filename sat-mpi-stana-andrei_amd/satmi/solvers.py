@@ -25,6 +25,7 @@ from typing import Dict, List, Optional, Tuple
 
 from . import _capi
 from .dpll import dpll_batch
+from .incremental import Solver  # noqa: F401  (the query loop: add_clause / solve(assumptions=...))
 
 Literal = int
 Clause = List[Literal]
