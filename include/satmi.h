@@ -901,7 +901,8 @@ uint64_t satmi_cdcl_sound_lds_bytes(int max_vars);
  *   level is above 0.  The core is therefore a first, then assumptions in
  *   descending trail position: a sublist of the assumptions as literals, [a]
  *   alone when -a holds at level 0, [a, -a] when the assumptions contradict
- *   each other.  It need not be minimal.
+ *   each other.  It need not be minimal (satmi_cdcl_shrink_batch_* below
+ *   shrinks it until it is).
  *   Limits: an instance with more than SATMI_CDCL_SOUND_MAX_VARS assumptions, or
  *   with an assumption literal 0, INT32_MIN or beyond inst_nvars[b], ends
  *   TOO_LARGE untouched; levels therefore stay below 2^16.  The assumptions are
@@ -1058,6 +1059,96 @@ int satmi_cdcl_carry_batch_host(int num_instances, const int32_t *h_inst_clause_
                                 const int32_t *h_carry_clause_begin, const int32_t *h_carry_lits,
                                 int32_t *h_kept_inst_begin, int32_t *h_kept_clause_begin, int64_t kept_clause_cap,
                                 int32_t *h_kept_lits, int64_t kept_lit_cap);
+
+/*
+ * Minimal failed-assumption cores: deletion-based minimisation with core
+ * refinement, the whole chain of an instance in one launch.
+ * satmi_cdcl_shrink_batch_device (csrc/cdcl_sound.hip, a fourth instantiation
+ * of the search kernel; the ones above keep their machine code) takes an
+ * instance of satmi_cdcl_carry_batch_device: formula F, assumptions a_1 .. a_k,
+ * conflict_limit, carried lemmas.  Its wavefront runs a chain of carrying
+ * searches on it; tests/cdcl_shrink_rows.py restates the chain in Python as a
+ * composition of the carrying rule.
+ *   Query 0 is the carrying search on the assumptions as given.  If it ends
+ *   anything but ASSUMED the instance ends there, and every output that the
+ *   carrying entry point has is that entry point's, word for word.
+ *   Otherwise let W be query 0's core in the order reported and p = 0.  While
+ *   p < |W|: the trial list is W without W[p], order kept, and the wavefront
+ *   runs the carrying search on F under the trial list.  That search carries
+ *   every non-empty record now in the region; the closing empty record of the
+ *   query before is dropped first, as carry_out drops it.  Activities, phases
+ *   and the conflict number that conflict_limit and the halving look at start
+ *   afresh, as the carry rule says of any resumed search, and the variables
+ *   that occur are those of F, of the records and of the trial list, as in any
+ *   carrying search under that list.  Then, as the trial ends
+ *     ASSUMED with core C: W becomes the trial list's members that are in C, in
+ *       W's order; p is unchanged.  (C comes out the refuted assumption first
+ *       and then by descending level, the trial list's order backwards.)
+ *     SAT: W[p] is necessary; p += 1.
+ *     LIMIT: W[p] is kept unproven; p += 1; the LIMIT-trial count goes up.
+ *     UNSAT (a conflict at level 0): F alone is unsatisfiable.  W becomes empty
+ *       and the chain ends: the instance ends UNSAT, its region closed by that
+ *       query's empty record.
+ *     FULL: the instance ends FULL with core_len 0.
+ *   The end: the instance is ASSUMED with core W.  The region holds every lemma
+ *   carried and learned by every query of the chain, in order, closed by one
+ *   empty record (the last query's when that ended ASSUMED, else one written
+ *   now); if that record does not fit the instance ends FULL.
+ *   The first p literals survive a refinement: x became necessary because F
+ *   with (W_then \ x) was satisfiable, every later W is a subset of W_then, so
+ *   x is in every core drawn from a later W.  Every trial removes a literal of
+ *   W or passes one, so there are at most |query 0's core| trials.
+ *   The proof: every lemma of every query follows from F alone (the argument
+ *   of the sound search).  The last ASSUMED query, whose core is W as a set,
+ *   left a lemma list from which unit propagation over F, the lemmas and W's
+ *   units reaches the empty clause, and lemmas added after it only help.  So
+ *   (F + W's unit clauses, the region's records) is a RUP refutation that
+ *   satmi_cdcl_assume_pack_device and the refutation check and trim read
+ *   unchanged.
+ *   Minimal: when no trial ended LIMIT, F with W less any one literal is
+ *   satisfiable; the SAT trials found those models, which are not returned.
+ *   Outputs: status; row_len / row_lits (only query 0's SAT writes a row);
+ *   core_len / core_lits (the final W; the words behind it, up to query 0's
+ *   core length and core_stride, are 0; core_stride may be 0: the refinement
+ *   does not read core_lits); carry_out (the non-empty records at the end).
+ *   counters are summed over the chain's queries, the highest level being their
+ *   maximum.  info is the final region's records and words, the closing record
+ *   or the record that did not fit included, and the flags.  shrink_info,
+ *   int64 [B x SATMI_CDCL_SHRINK_NWORDS]: the queries run (query 0 included),
+ *   the SAT trials, the ASSUMED trials, the LIMIT trials (non-zero: minimality
+ *   is not proven), the length of query 0's core (0 unless it ended ASSUMED), 0.
+ *   time_limit_s bounds the instance's whole chain from its first query: every
+ *   trial reached late ends LIMIT.
+ *   d_work_lits, int32, two words per assumption: instance b owns
+ *   [2 * assume_begin[b], 2 * assume_begin[b + 1]), only its wavefront touches
+ *   them, and their contents on return are unspecified.
+ * The host form is satmi_cdcl_carry_batch_host's with h_shrink_info [B x 6]
+ * (not NULL): the same checks before any HIP call, the same workspace, the same
+ * run-again from the input carry for the instances that ended FULL, the same
+ * packs for the proof and the kept lemmas.
+ */
+#define SATMI_CDCL_SHRINK_NWORDS 6
+int satmi_cdcl_shrink_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                   const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                   const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                   int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                   const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                   int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                   const int32_t *d_assume_begin, const int32_t *d_assume_lits, int32_t *d_core_len,
+                                   int32_t *d_core_lits, int core_stride, const int64_t *d_carry_in,
+                                   int64_t *d_carry_out, int32_t *d_work_lits, int64_t *d_shrink_info, void *stream);
+int satmi_cdcl_shrink_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                 const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                 const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                 int64_t room_cap, int32_t *h_status, int64_t *h_counters, int32_t *h_row_len,
+                                 int32_t *h_row_lits, int stride, int32_t *h_proof_inst_begin,
+                                 int32_t *h_proof_clause_begin, int64_t proof_clause_cap, int32_t *h_proof_lits,
+                                 int64_t proof_lit_cap, int64_t *h_info, int64_t *h_totals,
+                                 const int32_t *h_assume_begin, const int32_t *h_assume_lits, int32_t *h_core_len,
+                                 int32_t *h_core_lits, int core_stride, const int32_t *h_carry_inst_begin,
+                                 const int32_t *h_carry_clause_begin, const int32_t *h_carry_lits,
+                                 int32_t *h_kept_inst_begin, int32_t *h_kept_clause_begin, int64_t kept_clause_cap,
+                                 int32_t *h_kept_lits, int64_t kept_lit_cap, int64_t *h_shrink_info);
 
 /* Device-side span of the last DPLL launch on `stream`: enqueues (on that
  * stream, after the launch) a copy of two uint64 s_memrealtime ticks into

@@ -45,6 +45,13 @@
 //     touches anything, marks their variables as occurring and starts with
 //     `used` behind them; from then on they are learned clauses.  A third
 //     inclusion of the same text gives that search kernel.
+//   * Minimal cores (satmi_cdcl_shrink_batch_device, restated in
+//     tests/cdcl_shrink_rows.py): a fourth inclusion wraps the instance's body
+//     in the loop of a chain of queries.  After a query that ended ASSUMED the
+//     wave keeps the core in the caller's scratch, rebuilds the per-variable
+//     arrays as every query does, walks the region again as the next query's
+//     carry, and searches under the core less one literal; no wave waits for
+//     another, and nothing of the chain lives in LDS.
 //
 // Plain C++ and vector memory operations only.  The translation unit shares no
 // device code with any other kernel, whose machine code stays what it is.
@@ -106,6 +113,13 @@ struct CsAssumeArgs : CsArgs {
 struct CsCarryArgs : CsAssumeArgs {
     const int64_t *carry_in;
     int64_t *carry_out;                        // [B x 2]
+};
+
+// The same as a chain of queries that shrinks the core: instance b's scratch is
+// work_lits[2 * assume_begin[b] .. 2 * assume_begin[b + 1]), touched by its wave only.
+struct CsShrinkArgs : CsCarryArgs {
+    int32_t *work_lits;
+    int64_t *shrink_info;                      // [B x SATMI_CDCL_SHRINK_NWORDS]
 };
 
 struct CsWave {
@@ -285,9 +299,11 @@ __device__ __forceinline__ int64_t cs_incl_scan64(int64_t x) {
 // The search and the pack's scan, in both forms: cdcl_sound_search.inc is their
 // text.  The first inclusion gives the kernels of satmi_cdcl_sound_* as they
 // always were; the second the assumption-carrying ones of satmi_cdcl_assume_*;
-// the third the search of satmi_cdcl_carry_*, which starts from carried lemmas.
+// the third the search of satmi_cdcl_carry_*, which starts from carried lemmas;
+// the fourth the search of satmi_cdcl_shrink_*, a chain of such searches.
 #define CS_ASSUME 0
 #define CS_CARRY 0
+#define CS_SHRINK 0
 #define CS_SEARCH_KERNEL cdcl_sound_kernel
 #define CS_SEARCH_ARGS CsArgs
 #define CS_PACK_SCAN_KERNEL cdcl_sound_pack_scan_kernel
@@ -311,8 +327,16 @@ __device__ __forceinline__ int64_t cs_incl_scan64(int64_t x) {
 #define CS_SEARCH_KERNEL cdcl_carry_kernel
 #define CS_SEARCH_ARGS CsCarryArgs
 #include "cdcl_sound_search.inc"
+#undef CS_SHRINK
+#undef CS_SEARCH_KERNEL
+#undef CS_SEARCH_ARGS
+#define CS_SHRINK 1
+#define CS_SEARCH_KERNEL cdcl_shrink_kernel
+#define CS_SEARCH_ARGS CsShrinkArgs
+#include "cdcl_sound_search.inc"
 #undef CS_ASSUME
 #undef CS_CARRY
+#undef CS_SHRINK
 #undef CS_SEARCH_KERNEL
 #undef CS_SEARCH_ARGS
 
@@ -440,6 +464,7 @@ namespace {
 constexpr OomText CS_OOM{"satmi_cdcl_sound_batch_host", "split the batch"};
 constexpr OomText CS_ASSUME_OOM{"satmi_cdcl_assume_batch_host", "split the batch"};
 constexpr OomText CS_CARRY_OOM{"satmi_cdcl_carry_batch_host", "split the batch"};
+constexpr OomText CS_SHRINK_OOM{"satmi_cdcl_shrink_batch_host", "split the batch"};
 
 std::atomic<int> g_cs_grid{0}, g_cs_wpg{0};      // satmi_cdcl_sound_debug_grid
 std::atomic<int64_t> g_cs_room{0};               // satmi_cdcl_sound_debug_room
@@ -496,9 +521,15 @@ struct CsCarryDev {
     int64_t *out;
 };
 
+// The scratch and the chain's words of satmi_cdcl_shrink_batch_device.
+struct CsShrinkDev {
+    int32_t *work;
+    int64_t *info;
+};
+
 // The device forms: `as` = nullptr is satmi_cdcl_sound_batch_device, its kernels and all;
-// `cy` (with `as`) is satmi_cdcl_carry_batch_device.
-int cs_solve_device(const char *who, const CsAssumeIo *as, const CsCarryDev *cy, int num_instances, const int32_t *d_inst_clause_begin,
+// `cy` (with `as`) is satmi_cdcl_carry_batch_device; `sk` (with both) satmi_cdcl_shrink_batch_device.
+int cs_solve_device(const char *who, const CsAssumeIo *as, const CsCarryDev *cy, const CsShrinkDev *sk, int num_instances, const int32_t *d_inst_clause_begin,
                     const int32_t *d_clause_lit_begin, const int32_t *d_lits, const int32_t *d_inst_nvars,
                     int max_vars, int max_clause_len, int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
                     const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters, int32_t *d_row_len,
@@ -514,6 +545,7 @@ int cs_solve_device(const char *who, const CsAssumeIo *as, const CsCarryDev *cy,
     if (as && (!as->begin || !as->lits || !as->core_len || (as->core_stride > 0 && !as->core_lits)))
         return fail_arg(who, "null pointer");
     if (cy && !cy->out) return fail_arg(who, "null pointer");
+    if (sk && (!sk->work || !sk->info)) return fail_arg(who, "null pointer");
     if (max_vars > SATMI_CDCL_SOUND_MAX_VARS) return cs_too_large(who, max_vars);
     DeviceFacts facts;
     SATMI_TRY(device_facts(&facts));
@@ -555,6 +587,27 @@ int cs_solve_device(const char *who, const CsAssumeIo *as, const CsCarryDev *cy,
     const int grid = batch_grid(facts, lds_bytes, 0, 64 * wpg, wgs, g_cs_grid);
     const bool long_form = max_clause_len <= 0 || max_clause_len > CS_SHORT_MAX;
     hipStream_t s = (hipStream_t)stream;
+    if (sk) {
+        CsShrinkArgs SA{};
+        static_cast<CsArgs &>(SA) = A;
+        SA.assume_begin = as->begin;
+        SA.assume_lits = as->lits;
+        SA.core_len = as->core_len;
+        SA.core_lits = as->core_lits;
+        SA.core_stride = as->core_stride;
+        SA.carry_in = cy->in;
+        SA.carry_out = cy->out;
+        SA.work_lits = sk->work;
+        SA.shrink_info = sk->info;
+        const void *fn = long_form ? (const void *)cdcl_shrink_kernel<true> : (const void *)cdcl_shrink_kernel<false>;
+        SATMI_TRY(batch_allow_lds(fn, lds_bytes));
+        if (long_form)
+            hipLaunchKernelGGL(cdcl_shrink_kernel<true>, dim3(grid), dim3(64 * wpg), lds_bytes, s, SA);
+        else
+            hipLaunchKernelGGL(cdcl_shrink_kernel<false>, dim3(grid), dim3(64 * wpg), lds_bytes, s, SA);
+        SATMI_HIP(hipGetLastError());
+        return SATMI_OK;
+    }
     if (cy) {
         CsCarryArgs CA{};
         static_cast<CsArgs &>(CA) = A;
@@ -645,7 +698,7 @@ extern "C" int satmi_cdcl_sound_batch_device(int num_instances, const int32_t *d
                                              const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
                                              int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
                                              void *stream) {
-    return cs_solve_device("satmi_cdcl_sound_batch_device", nullptr, nullptr, num_instances, d_inst_clause_begin,
+    return cs_solve_device("satmi_cdcl_sound_batch_device", nullptr, nullptr, nullptr, num_instances, d_inst_clause_begin,
                            d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
                            time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
                            d_info, stream);
@@ -661,7 +714,7 @@ extern "C" int satmi_cdcl_assume_batch_device(int num_instances, const int32_t *
                                               int32_t *d_core_len, int32_t *d_core_lits, int core_stride,
                                               void *stream) {
     const CsAssumeIo as{d_assume_begin, d_assume_lits, d_core_len, d_core_lits, core_stride};
-    return cs_solve_device("satmi_cdcl_assume_batch_device", &as, nullptr, num_instances, d_inst_clause_begin,
+    return cs_solve_device("satmi_cdcl_assume_batch_device", &as, nullptr, nullptr, num_instances, d_inst_clause_begin,
                            d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
                            time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
                            d_info, stream);
@@ -678,7 +731,26 @@ extern "C" int satmi_cdcl_carry_batch_device(int num_instances, const int32_t *d
                                              const int64_t *d_carry_in, int64_t *d_carry_out, void *stream) {
     const CsAssumeIo as{d_assume_begin, d_assume_lits, d_core_len, d_core_lits, core_stride};
     const CsCarryDev cy{d_carry_in, d_carry_out};
-    return cs_solve_device("satmi_cdcl_carry_batch_device", &as, &cy, num_instances, d_inst_clause_begin,
+    return cs_solve_device("satmi_cdcl_carry_batch_device", &as, &cy, nullptr, num_instances, d_inst_clause_begin,
+                           d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
+                           time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
+                           d_info, stream);
+}
+
+extern "C" int satmi_cdcl_shrink_batch_device(int num_instances, const int32_t *d_inst_clause_begin,
+                                              const int32_t *d_clause_lit_begin, const int32_t *d_lits,
+                                              const int32_t *d_inst_nvars, int max_vars, int max_clause_len,
+                                              int64_t conflict_limit, double time_limit_s, int32_t *d_lemmas,
+                                              const int64_t *d_lemma_begin, int32_t *d_status, int64_t *d_counters,
+                                              int32_t *d_row_len, int32_t *d_row_lits, int stride, int64_t *d_info,
+                                              const int32_t *d_assume_begin, const int32_t *d_assume_lits,
+                                              int32_t *d_core_len, int32_t *d_core_lits, int core_stride,
+                                              const int64_t *d_carry_in, int64_t *d_carry_out, int32_t *d_work_lits,
+                                              int64_t *d_shrink_info, void *stream) {
+    const CsAssumeIo as{d_assume_begin, d_assume_lits, d_core_len, d_core_lits, core_stride};
+    const CsCarryDev cy{d_carry_in, d_carry_out};
+    const CsShrinkDev sk{d_work_lits, d_shrink_info};
+    return cs_solve_device("satmi_cdcl_shrink_batch_device", &as, &cy, &sk, num_instances, d_inst_clause_begin,
                            d_clause_lit_begin, d_lits, d_inst_nvars, max_vars, max_clause_len, conflict_limit,
                            time_limit_s, d_lemmas, d_lemma_begin, d_status, d_counters, d_row_len, d_row_lits, stride,
                            d_info, stream);
@@ -748,8 +820,10 @@ struct CsCarryIo {
 };
 
 // The host forms: `as` = nullptr is satmi_cdcl_sound_batch_host, else its host arrays;
-// `cy` (with `as`) is satmi_cdcl_carry_batch_host, whose h_totals has four words.
-int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, const CsCarryIo *cy, int num_instances,
+// `cy` (with `as`) is satmi_cdcl_carry_batch_host, whose h_totals has four words;
+// `shrink` (with both) is satmi_cdcl_shrink_batch_host, which fills h_shrink_info.
+int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, const CsCarryIo *cy, bool shrink,
+                  int64_t *h_shrink_info, int num_instances,
                   const int32_t *h_inst_clause_begin, const int32_t *h_clause_lit_begin, const int32_t *h_lits,
                   const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s, int64_t room_cap,
                   int32_t *h_status, int64_t *h_counters, int32_t *h_row_len, int32_t *h_row_lits, int stride,
@@ -769,7 +843,7 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, con
     const bool outs = h_inst_nvars && h_status && h_counters && h_row_len && h_row_lits && h_proof_inst_begin &&
                       h_proof_clause_begin && h_proof_lits && h_totals &&
                       (!as || (as->begin && as->core_len && (as->core_stride == 0 || as->core_lits))) &&
-                      (!kept || (cy->kib && cy->kcb && cy->klits));
+                      (!kept || (cy->kib && cy->kcb && cy->klits)) && (!shrink || h_shrink_info);
     if (const char *bad = batch_csr_check(num_instances, h_inst_clause_begin, h_clause_lit_begin, h_lits, own, outs,
                                           &sh, nv.data()))
         return fail_arg(who, bad);
@@ -849,6 +923,8 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, con
     const size_t o_kib = cy ? cv.take(4 * (B + 1)) : 0;
     const size_t o_kcb = cy ? cv.take(4 * (kccap + 1)) : 0;
     const size_t o_klits = cy ? cv.take(4 * std::max<size_t>(klcap, 1)) : 0;
+    const size_t o_work = shrink ? cv.take(8 * (size_t)std::max(Atot, 1)) : 0;   // two words per assumption
+    const size_t o_sinfo = shrink ? cv.take(8 * B * SATMI_CDCL_SHRINK_NWORDS) : 0;
     SATMI_TRY(wk.block.reserve(cv.at, oom));
     const Staged d{wk.block.as<unsigned char>(), s};
     SATMI_TRY(d.up(o_icb, h_inst_clause_begin, 4 * (B + 1)));
@@ -880,6 +956,7 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, con
         SATMI_TRY(d.up(o_cin, hc, cnt));
         dcy = CsCarryDev{d.at<const int64_t>(o_cin), d.at<int64_t>(o_cout)};
     }
+    const CsShrinkDev dsk{shrink ? d.at<int32_t>(o_work) : nullptr, shrink ? d.at<int64_t>(o_sinfo) : nullptr};
 
     // ---- solve; again with four times the room for the instances that ended FULL, up to the caller's cap
     const int64_t dbg_room = g_cs_room.load();
@@ -902,10 +979,11 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, con
             SATMI_HIP(hipGetLastError());
         }
         SATMI_TRY(cs_solve_device(
-            cy   ? "satmi_cdcl_carry_batch_device"
-            : as ? "satmi_cdcl_assume_batch_device"
-                 : "satmi_cdcl_sound_batch_device",
-            as ? &das : nullptr, cy ? &dcy : nullptr, num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
+            shrink ? "satmi_cdcl_shrink_batch_device"
+            : cy   ? "satmi_cdcl_carry_batch_device"
+            : as   ? "satmi_cdcl_assume_batch_device"
+                   : "satmi_cdcl_sound_batch_device",
+            as ? &das : nullptr, cy ? &dcy : nullptr, shrink ? &dsk : nullptr, num_instances, d.at<const int32_t>(o_icb), d.at<const int32_t>(o_clb), d.at<const int32_t>(o_lits),
             d.at<const int32_t>(o_nv), max_vars, C > 0 ? sh.max_len : 0, conflict_limit, time_limit_s,
             wk.lemmas.as<int32_t>(), d.at<const int64_t>(o_lb), d.at<int32_t>(o_st), d.at<int64_t>(o_ctr),
             d.at<int32_t>(o_rl), d.at<int32_t>(o_row), stride, d.at<int64_t>(o_info), s));
@@ -944,6 +1022,7 @@ int cs_batch_host(const char *who, const OomText *oom, const CsAssumeIo *as, con
         SATMI_TRY(d.down(as->core_len, o_cl, 4 * B));
         SATMI_TRY(d.down(as->core_lits, o_core, 4 * B * cstride));
     }
+    if (shrink) SATMI_TRY(d.down(h_shrink_info, o_sinfo, 8 * B * SATMI_CDCL_SHRINK_NWORDS));
     SATMI_HIP(hipStreamSynchronize(s));
     lease.ok = true;   // the stream is drained; the next call trusts nothing of the workspace
     const bool fits = totals[0] <= proof_clause_cap && totals[1] <= proof_lit_cap;
@@ -975,7 +1054,7 @@ extern "C" int satmi_cdcl_sound_batch_host(int num_instances, const int32_t *h_i
                                            int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
                                            int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
                                            int64_t *h_info, int64_t *h_totals) {
-    return cs_batch_host("satmi_cdcl_sound_batch_host", &CS_OOM, nullptr, nullptr, num_instances, h_inst_clause_begin,
+    return cs_batch_host("satmi_cdcl_sound_batch_host", &CS_OOM, nullptr, nullptr, false, nullptr, num_instances, h_inst_clause_begin,
                          h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
                          h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
                          proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
@@ -992,7 +1071,7 @@ extern "C" int satmi_cdcl_assume_batch_host(int num_instances, const int32_t *h_
                                             const int32_t *h_assume_lits, int32_t *h_core_len, int32_t *h_core_lits,
                                             int core_stride) {
     const CsAssumeIo as{h_assume_begin, h_assume_lits, h_core_len, h_core_lits, core_stride};
-    return cs_batch_host("satmi_cdcl_assume_batch_host", &CS_ASSUME_OOM, &as, nullptr, num_instances, h_inst_clause_begin,
+    return cs_batch_host("satmi_cdcl_assume_batch_host", &CS_ASSUME_OOM, &as, nullptr, false, nullptr, num_instances, h_inst_clause_begin,
                          h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
                          h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
                          proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
@@ -1014,8 +1093,31 @@ extern "C" int satmi_cdcl_carry_batch_host(int num_instances, const int32_t *h_i
     const CsAssumeIo as{h_assume_begin, h_assume_lits, h_core_len, h_core_lits, core_stride};
     const CsCarryIo cy{h_carry_inst_begin, h_carry_clause_begin, h_carry_lits, h_kept_inst_begin,
                        h_kept_clause_begin, kept_clause_cap, h_kept_lits, kept_lit_cap};
-    return cs_batch_host("satmi_cdcl_carry_batch_host", &CS_CARRY_OOM, &as, &cy, num_instances, h_inst_clause_begin,
+    return cs_batch_host("satmi_cdcl_carry_batch_host", &CS_CARRY_OOM, &as, &cy, false, nullptr, num_instances, h_inst_clause_begin,
                          h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s, room_cap, h_status,
                          h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin, h_proof_clause_begin,
                          proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
+}
+
+extern "C" int satmi_cdcl_shrink_batch_host(int num_instances, const int32_t *h_inst_clause_begin,
+                                            const int32_t *h_clause_lit_begin, const int32_t *h_lits,
+                                            const int32_t *h_inst_nvars, int64_t conflict_limit, double time_limit_s,
+                                            int64_t room_cap, int32_t *h_status, int64_t *h_counters,
+                                            int32_t *h_row_len, int32_t *h_row_lits, int stride,
+                                            int32_t *h_proof_inst_begin, int32_t *h_proof_clause_begin,
+                                            int64_t proof_clause_cap, int32_t *h_proof_lits, int64_t proof_lit_cap,
+                                            int64_t *h_info, int64_t *h_totals, const int32_t *h_assume_begin,
+                                            const int32_t *h_assume_lits, int32_t *h_core_len, int32_t *h_core_lits,
+                                            int core_stride, const int32_t *h_carry_inst_begin,
+                                            const int32_t *h_carry_clause_begin, const int32_t *h_carry_lits,
+                                            int32_t *h_kept_inst_begin, int32_t *h_kept_clause_begin,
+                                            int64_t kept_clause_cap, int32_t *h_kept_lits, int64_t kept_lit_cap,
+                                            int64_t *h_shrink_info) {
+    const CsAssumeIo as{h_assume_begin, h_assume_lits, h_core_len, h_core_lits, core_stride};
+    const CsCarryIo cy{h_carry_inst_begin, h_carry_clause_begin, h_carry_lits, h_kept_inst_begin,
+                       h_kept_clause_begin, kept_clause_cap, h_kept_lits, kept_lit_cap};
+    return cs_batch_host("satmi_cdcl_shrink_batch_host", &CS_SHRINK_OOM, &as, &cy, true, h_shrink_info, num_instances,
+                         h_inst_clause_begin, h_clause_lit_begin, h_lits, h_inst_nvars, conflict_limit, time_limit_s,
+                         room_cap, h_status, h_counters, h_row_len, h_row_lits, stride, h_proof_inst_begin,
+                         h_proof_clause_begin, proof_clause_cap, h_proof_lits, proof_lit_cap, h_info, h_totals);
 }

@@ -15,6 +15,12 @@
 // the instance carries an ordered list of assumption literals (CsAssumeArgs),
 // read from the caller's arrays where they lie; level i <= k belongs to
 // assumption i.  The lines of the carrying form are under #if CS_CARRY.
+// A fourth inclusion with CS_SHRINK 1 (and CS_ASSUME, CS_CARRY 1; CsShrinkArgs)
+// is satmi_cdcl_shrink_batch_device's kernel: the wave runs the instance's body
+// as a chain of queries, query 0 as the carrying form does and then one trial
+// per literal of the core, each under the core less that literal and carrying
+// every lemma in the region.  Its lines are under #if CS_SHRINK, which is 0 in
+// the three inclusions before it.
 template <bool LONG>
 __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
     extern __shared__ __attribute__((aligned(16))) uint32_t cs_lds[];
@@ -75,6 +81,30 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
         if (A.carry_in) {
             cin_r = A.carry_in[2 * b];
             cin_w = A.carry_in[2 * b + 1];
+        }
+#endif
+#if CS_SHRINK
+        // ---- the chain: query 0 under the assumptions as given, then trials under W less W[p].
+        // The instance's scratch: W in its first na0 words; behind them the trial list while a
+        // trial searches, and the core of a final analysis as it is collected (the list is
+        // dead by then).  Every query but the first re-walks the region as its carry.
+        const int na0 = na;
+        int32_t *const wl = A.work_lits + 2 * (int64_t)A.assume_begin[b], *const tl = wl + na0;
+        int nw = 0, wp = 0, core0 = 0, nq = 0, n_sat = 0, n_assumed = 0, n_limit = 0;
+        int64_t s_conflicts = 0, s_decisions = 0, s_props = 0, s_rounds = 0, s_learned = 0, s_learned_lits = 0, s_top = 0;
+        for (int q = 0; q <= na0; ++q) {   // (a trial drops a literal of W or passes one: at most |W| <= na0 of them)
+        if (q > 0) {
+            // the trial list; the carry is what lies in the region without its closing record
+            for (int j = ln; j < nw - 1; j += 64) tl[j] = wl[j + (j >= wp ? 1 : 0)];
+            assume = tl;
+            na = nw - 1;
+            cin_r += learned;
+            cin_w = w.used - (status == SATMI_CDCL_SOUND_ASSUMED ? 1 : 0);
+            status = CS_RUNNING;
+            conflicts = decisions = props = rounds = learned = learned_lits = top = 0;
+            w.trail_len = w.ncand = w.cur = 0;
+            core = 0;
+            wave_sync();
         }
 #endif
         if (status == CS_RUNNING) {
@@ -318,6 +348,9 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
                         int32_t *cp = A.core_lits + b * (int64_t)A.core_stride;
                         if (ln == 0) {
                             if (A.core_stride > 0) cp[0] = a;
+#if CS_SHRINK
+                            tl[0] = a;   // (na0 >= 1 here: an assumption was read)
+#endif
                             if (w.level[av] > 0) atomicOr(&w.seen[av >> 5], 1u << (av & 31u));
                         }
                         core = 1;
@@ -343,6 +376,9 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
                             --idx;
                             if (code < 0) {   // no reason: at these levels an assumption
                                 if (ln == 0 && core < A.core_stride) cp[core] = cs_dec(pe);
+#if CS_SHRINK
+                                if (ln == 0 && core < na) tl[core] = cs_dec(pe);   // (one per level below this one: always so)
+#endif
                                 ++core;
                             } else if (code != CS_NONE) {   // the others of its reason, above level 0
                                 int len;
@@ -388,6 +424,12 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
             }
             best = wave_max_u32(best);
             if (best == 0u) {   // SAT: every variable of the formula is assigned
+#if CS_SHRINK
+                if (q > 0) {   // a trial's model is not returned
+                    status = SATMI_CDCL_SOUND_SAT;
+                    break;
+                }
+#endif
                 int k = 0;
                 for (int v0 = 1; v0 <= w.nv; v0 += 64) {
                     const int v = v0 + ln;
@@ -423,6 +465,55 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
             }
         }
         if (status == CS_RUNNING) status = SATMI_CDCL_SOUND_LIMIT;   // the pass bound (never by the rule)
+#if CS_SHRINK
+        ++nq;
+        s_conflicts += conflicts;
+        s_decisions += decisions;
+        s_props += props;
+        s_rounds += rounds;
+        s_learned += learned;
+        s_learned_lits += learned_lits;
+        s_top = max(s_top, top);
+        wave_sync();   // lane 0's core words, before the lanes read them
+        if (status == SATMI_CDCL_SOUND_ASSUMED) {
+            // Query 0's core is W in the order reported.  A trial's core comes out the
+            // refuted assumption first and then by descending level, which is the trial
+            // list's order backwards: W is those literals turned round, still in W's order.
+            core = min(core, na);   // (na0 at query 0, nw - 1 after: the words collected)
+            for (int j = ln; j < core; j += 64) wl[j] = tl[q == 0 ? j : core - 1 - j];
+            nw = core;
+            if (q == 0) core0 = core;
+            else ++n_assumed;
+            wave_sync();
+        } else if (q > 0 && status == SATMI_CDCL_SOUND_SAT) {
+            ++n_sat;
+            ++wp;
+        } else if (q > 0 && status == SATMI_CDCL_SOUND_LIMIT) {
+            ++n_limit;
+            ++wp;
+        } else {   // query 0 ended otherwise; a trial refuted F alone or filled the region
+            break;
+        }
+        if (wp >= nw) break;
+        }
+        if (nq > 1 && (status == SATMI_CDCL_SOUND_SAT || status == SATMI_CDCL_SOUND_LIMIT || status == SATMI_CDCL_SOUND_ASSUMED)) {
+            // ---- the end: ASSUMED with core W, the region closed by one empty record
+            if (status != SATMI_CDCL_SOUND_ASSUMED) {
+                ++records;
+                ++words;
+                if (w.used + 1 <= w.room) {
+                    if (ln == 0) w.rec[w.used] = 0;
+                    ++w.used;
+                    status = SATMI_CDCL_SOUND_ASSUMED;
+                } else {
+                    status = SATMI_CDCL_SOUND_FULL;
+                }
+            }
+            core = nw;
+            int32_t *cp = A.core_lits + b * (int64_t)A.core_stride;
+            for (int j = ln; j < min(core0, A.core_stride); j += 64) cp[j] = j < nw ? wl[j] : 0;   // (0 behind W, over query 0's core)
+        }
+#endif
         const bool trunc = status == SATMI_CDCL_SOUND_FULL;
         if (ln == 0) {
             A.status[b] = status;
@@ -439,6 +530,22 @@ __global__ void __launch_bounds__(256) CS_SEARCH_KERNEL(CS_SEARCH_ARGS A) {
             A.carry_out[2 * b + 1] = bad_carry ? 0 : ran ? w.used - (closed ? 1 : 0) : cin_w;
 #endif
         }
+#if CS_SHRINK
+        if (ln < SATMI_CDCL_SHRINK_NWORDS)
+            A.shrink_info[b * SATMI_CDCL_SHRINK_NWORDS + ln] = ln == 0   ? nq
+                                                               : ln == 1 ? n_sat
+                                                               : ln == 2 ? n_assumed
+                                                               : ln == 3 ? n_limit
+                                                               : ln == 4 ? core0
+                                                                         : 0;
+        conflicts = s_conflicts;   // the counters of the chain
+        decisions = s_decisions;
+        props = s_props;
+        rounds = s_rounds;
+        learned = s_learned;
+        learned_lits = s_learned_lits;
+        top = s_top;
+#endif
         if (ln < SATMI_CDCL_SOUND_NCOUNTERS)
             A.counters[b * SATMI_CDCL_SOUND_NCOUNTERS + ln] = ln == 0   ? conflicts
                                                               : ln == 1 ? decisions

@@ -63,6 +63,9 @@ CDCL_SOUND_WORDS = ("records", "region_words", "flags", "first_literal")
 CDCL_SOUND_TRUNCATED = 1
 CDCL_SOUND_BAD_CARRY = 2   # satmi_cdcl_carry_*: the carried records were malformed
 CDCL_SOUND_MAX_VARS = 8191
+# satmi_cdcl_shrink_*: the int64 words of the chain per instance
+CDCL_SHRINK_NWORDS = 6
+CDCL_SHRINK_WORDS = ("queries", "sat_trials", "assumed_trials", "limit_trials", "first_core", "reserved")
 
 # exported symbols, checked by tests/test_capi_symbols.py against include/satmi.h
 EXPORTED = (
@@ -87,6 +90,7 @@ EXPORTED = (
     "satmi_cdcl_sound_debug_grid", "satmi_cdcl_sound_debug_room", "satmi_cdcl_sound_lds_bytes",
     "satmi_cdcl_assume_batch_device", "satmi_cdcl_assume_pack_device", "satmi_cdcl_assume_batch_host",
     "satmi_cdcl_carry_batch_device", "satmi_cdcl_carry_pack_device", "satmi_cdcl_carry_batch_host",
+    "satmi_cdcl_shrink_batch_device", "satmi_cdcl_shrink_batch_host",
 )
 
 
@@ -260,6 +264,10 @@ def load():
         [ctypes.c_int] + [i32p] * 4 + [ctypes.c_int64, ctypes.c_double, ctypes.c_int64]
         + [i32p, i64p, i32p, i32p, ctypes.c_int] + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64, i64p, i64p]
         + [i32p] * 4 + [ctypes.c_int] + [i32p] * 3 + [i32p, i32p, ctypes.c_int64, i32p, ctypes.c_int64])
+    L.satmi_cdcl_shrink_batch_device.argtypes = (
+        [ctypes.c_int] + [vp] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_double] + [vp] * 6
+        + [ctypes.c_int, vp] + [vp] * 4 + [ctypes.c_int, vp, vp, vp, vp, vp])
+    L.satmi_cdcl_shrink_batch_host.argtypes = L.satmi_cdcl_carry_batch_host.argtypes + [i64p]
     L.satmi_cdcl_sound_debug_grid.argtypes = [ctypes.c_int, ctypes.c_int]
     L.satmi_cdcl_sound_debug_room.argtypes = [ctypes.c_int64]
     L.satmi_cdcl_sound_lds_bytes.restype = ctypes.c_uint64

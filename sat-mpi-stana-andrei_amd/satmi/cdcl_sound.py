@@ -247,14 +247,10 @@ def pack_carry(carry, num_instances):
     return cib, ccb, np.array(flat or [0], dtype=np.int32), top
 
 
-def cdcl_carry_packed(batch, assume_begin, assume_lits, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0,
-                      room=None, core_stride=None, kept_room=None):
-    """satmi_cdcl_carry_batch_host on a CnfBatch whose inst_nvars cover the variables of the
-    assumptions and of the carried clauses; `carry` = the triple (inst_begin, clause_begin,
-    lits) of pack_carry, or None.  Returns cdcl_assume_packed's eight and the kept lemmas as a
-    CnfBatch: "formula" b of it is what the next query on formula b carries, whatever this
-    one's status.  `kept_room` = (lemmas, literals) the first call's kept arrays hold; like the
-    proof's, kept arrays that are outgrown are asked for again with 4x the room."""
+def _carry_packed(shrink, batch, assume_begin, assume_lits, carry, conflict_limit, time_limit, room_cap, room,
+                  core_stride, kept_room):
+    """The host forms with carried lemmas: satmi_cdcl_carry_batch_host, or with `shrink`
+    satmi_cdcl_shrink_batch_host, whose words per formula are the tenth value returned."""
     L = _capi.load()
     _capi.require_gpu()
     B = batch.num_instances
@@ -272,6 +268,7 @@ def cdcl_carry_packed(batch, assume_begin, assume_lits, carry=None, conflict_lim
     core_len = np.zeros(B, dtype=np.int32)
     core_lits = np.zeros((B, max(core_stride, 1)), dtype=np.int32)
     info = np.zeros((B, _capi.CDCL_SOUND_NWORDS), dtype=np.int64)
+    words = np.zeros((B, _capi.CDCL_SHRINK_NWORDS), dtype=np.int64)
     totals = np.zeros(4, dtype=np.int64)
     pib = np.zeros(B + 1, dtype=np.int32)
     kib = np.zeros(B + 1, dtype=np.int32)
@@ -279,19 +276,20 @@ def cdcl_carry_packed(batch, assume_begin, assume_lits, carry=None, conflict_lim
     carried = (0, 0) if carry is None else (int(cib[-1] - cib[0]), int(ccb[cib[-1]] - ccb[cib[0]]))
     kccap, klcap = kept_room if kept_room is not None else (ccap + carried[0], lcap + carried[1])
     i64 = ctypes.c_int64
+    who = "satmi_cdcl_shrink_batch_host" if shrink else "satmi_cdcl_carry_batch_host"
     while True:
         pcb = np.zeros(ccap + 1, dtype=np.int32)
         plits = np.zeros(lcap, dtype=np.int32)
         kcb = np.zeros(kccap + 1, dtype=np.int32)
         klits = np.zeros(max(klcap, 1), dtype=np.int32)
-        rc = L.satmi_cdcl_carry_batch_host(
+        rc = getattr(L, who)(
             B, _p(batch.inst_clause_begin), _p(batch.clause_lit_begin), _p(batch.lits), _p(batch.inst_nvars),
             int(conflict_limit), float(time_limit), int(room_cap), _p(status), _p(counters, i64), _p(row_len),
             _p(row_lits), int(stride), _p(pib), _p(pcb), int(ccap), _p(plits), int(lcap), _p(info, i64),
             _p(totals, i64), _p(assume_begin), _p(assume_lits), _p(core_len), _p(core_lits), int(core_stride),
             None if cib is None else _p(cib), None if ccb is None else _p(ccb), None if clits is None else _p(clits),
-            _p(kib), _p(kcb), int(kccap), _p(klits), int(klcap))
-        _capi.check(rc, "satmi_cdcl_carry_batch_host")
+            _p(kib), _p(kcb), int(kccap), _p(klits), int(klcap), *((_p(words, i64),) if shrink else ()))
+        _capi.check(rc, who)
         if B == 0 or (int(totals[0]) <= ccap and int(totals[1]) <= lcap and
                       int(totals[2]) <= kccap and int(totals[3]) <= klcap):
             break
@@ -304,27 +302,32 @@ def cdcl_carry_packed(batch, assume_begin, assume_lits, carry=None, conflict_lim
     zeros = np.zeros(B, dtype=np.int32)
     proof = CnfBatch(pib, pcb[:P + 1].copy(), plits[:max(int(pcb[P]), 1)].copy(), zeros)
     kept = CnfBatch(kib, kcb[:K + 1].copy(), klits[:max(int(kcb[K]), 1)].copy(), zeros)
-    return status, counters, row_len, row_lits, proof, info, core_len, core_lits[:, :core_stride], kept
+    return status, counters, row_len, row_lits, proof, info, core_len, core_lits[:, :core_stride], kept, words
 
 
-def cdcl_carry_batch(formulas, assumptions, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0, room=None,
-                     core_stride=None, kept_room=None):
-    """Sound CDCL on `formulas` under `assumptions`, formula b starting with the clauses
-    `carry[b]` as learned clauses (None = nothing carried anywhere): lemmas an earlier query
-    on the same formula, or on a subset of its clauses, kept.  cdcl_assume_batch's dict per
-    formula (with "flags", the info flags) plus "kept", the list of clauses to carry into the
-    next query: the carried ones and those this query learned, whatever its status.  With
-    "sat" False, "proof" holds the carried lemmas too: they are part of the refutation, and
-    that they follow from the formula is the caller's claim, which check_refutations tests."""
+def cdcl_carry_packed(batch, assume_begin, assume_lits, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0,
+                      room=None, core_stride=None, kept_room=None):
+    """satmi_cdcl_carry_batch_host on a CnfBatch whose inst_nvars cover the variables of the
+    assumptions and of the carried clauses; `carry` = the triple (inst_begin, clause_begin,
+    lits) of pack_carry, or None.  Returns cdcl_assume_packed's eight and the kept lemmas as a
+    CnfBatch: "formula" b of it is what the next query on formula b carries, whatever this
+    one's status.  `kept_room` = (lemmas, literals) the first call's kept arrays hold; like the
+    proof's, kept arrays that are outgrown are asked for again with 4x the room."""
+    return _carry_packed(False, batch, assume_begin, assume_lits, carry, conflict_limit, time_limit, room_cap, room,
+                         core_stride, kept_room)[:9]
+
+
+def _carry_batch(shrink, formulas, assumptions, carry, conflict_limit, time_limit, room_cap, room, core_stride,
+                 kept_room):
     batch = formulas if isinstance(formulas, CnfBatch) else pack(formulas)
     B = batch.num_instances
     begin, lits, top = pack_assumptions(assumptions, B)
     cib, ccb, clits, ctop = pack_carry(carry, B)
     batch = CnfBatch(batch.inst_clause_begin, batch.clause_lit_begin, batch.lits,
                      np.maximum(np.maximum(np.asarray(batch.inst_nvars, dtype=np.int32), top), ctop))
-    status, counters, row_len, row_lits, proof, info, core_len, core_lits, kept = cdcl_carry_packed(
-        batch, begin, lits, None if carry is None else (cib, ccb, clits), conflict_limit, time_limit, room_cap, room,
-        core_stride, kept_room)
+    status, counters, row_len, row_lits, proof, info, core_len, core_lits, kept, words = _carry_packed(
+        shrink, batch, begin, lits, None if carry is None else (cib, ccb, clits), conflict_limit, time_limit, room_cap,
+        room, core_stride, kept_room)
     out = []
     for b in range(B):
         st = int(status[b])
@@ -338,7 +341,22 @@ def cdcl_carry_batch(formulas, assumptions, carry=None, conflict_limit=0, time_l
                     "core_len": int(core_len[b]),
                     "records": int(info[b, 0]), "region_words": int(info[b, 1]), "flags": int(info[b, 2]),
                     "kept": [list(c) for c in kept.instance(b)]})
+        if shrink:
+            out[-1]["shrink"] = dict(zip(_capi.CDCL_SHRINK_WORDS, map(int, words[b])))
     return out
+
+
+def cdcl_carry_batch(formulas, assumptions, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0, room=None,
+                     core_stride=None, kept_room=None):
+    """Sound CDCL on `formulas` under `assumptions`, formula b starting with the clauses
+    `carry[b]` as learned clauses (None = nothing carried anywhere): lemmas an earlier query
+    on the same formula, or on a subset of its clauses, kept.  cdcl_assume_batch's dict per
+    formula (with "flags", the info flags) plus "kept", the list of clauses to carry into the
+    next query: the carried ones and those this query learned, whatever its status.  With
+    "sat" False, "proof" holds the carried lemmas too: they are part of the refutation, and
+    that they follow from the formula is the caller's claim, which check_refutations tests."""
+    return _carry_batch(False, formulas, assumptions, carry, conflict_limit, time_limit, room_cap, room, core_stride,
+                        kept_room)
 
 
 def cdcl_carry_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clause_len, lemmas, lemma_begin,
@@ -361,3 +379,42 @@ def carry_pack_device(num_instances, lemmas, lemma_begin, carry, kept_icb, kept_
         int(num_instances), lemmas, lemma_begin, carry, kept_icb, kept_clb, int(kept_clause_cap), kept_lits,
         int(kept_lit_cap), totals, stream)
     _capi.check(rc, "satmi_cdcl_carry_pack_device")
+
+
+# ---- minimal cores (satmi_cdcl_shrink_*): the chain of trial queries of every formula in one launch
+def cdcl_shrink_packed(batch, assume_begin, assume_lits, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0,
+                       room=None, core_stride=None, kept_room=None):
+    """satmi_cdcl_shrink_batch_host: cdcl_carry_packed's arguments and its nine values, the core
+    being the minimised one and the counters the chain's, and shrink int64 [B, 6]:
+    _capi.CDCL_SHRINK_WORDS."""
+    return _carry_packed(True, batch, assume_begin, assume_lits, carry, conflict_limit, time_limit, room_cap, room,
+                         core_stride, kept_room)
+
+
+def cdcl_shrink_batch(formulas, assumptions, carry=None, conflict_limit=0, time_limit=0.0, room_cap=0, room=None,
+                      core_stride=None, kept_room=None):
+    """cdcl_carry_batch where a formula that is unsatisfiable under its assumptions gets a minimal
+    core: after the first query one trial query per core literal runs under the core less that
+    literal, each carrying every lemma so far, and a literal stays when its trial is satisfiable
+    (or reaches conflict_limit).  cdcl_carry_batch's dict per formula, "core" being the shrunk
+    core in the first query's order, "proof" and "kept" the lemmas of the whole chain, the
+    counters its sums, and "shrink" the chain's words by name (_capi.CDCL_SHRINK_WORDS): with
+    "limit_trials" 0 the core less any one literal is satisfiable with the formula.  A formula
+    that a trial refutes without assumptions ends CDCL_SOUND_UNSAT with the core []."""
+    return _carry_batch(True, formulas, assumptions, carry, conflict_limit, time_limit, room_cap, room, core_stride,
+                        kept_room)
+
+
+def cdcl_shrink_device(num_instances, icb, clb, lits, inst_nvars, max_vars, max_clause_len, lemmas, lemma_begin,
+                       status, counters, row_len, row_lits, stride, info, assume_begin, assume_lits, core_len,
+                       core_lits, core_stride, carry_in, carry_out, work_lits, shrink_info, conflict_limit=0,
+                       time_limit=0.0, stream=None):
+    """satmi_cdcl_shrink_batch_device on device pointers (ints, e.g. a tensor's data_ptr();
+    `carry_in` may be None, or the same array as `carry_out`; `work_lits` = two int32 words per
+    assumption, `shrink_info` = six int64 words per formula); one launch, asynchronous on `stream`."""
+    rc = _capi.load().satmi_cdcl_shrink_batch_device(
+        int(num_instances), icb, clb, lits, inst_nvars, int(max_vars), int(max_clause_len), int(conflict_limit),
+        float(time_limit), lemmas, lemma_begin, status, counters, row_len, row_lits, int(stride), info,
+        assume_begin, assume_lits, core_len, core_lits, int(core_stride), carry_in, carry_out, work_lits, shrink_info,
+        stream)
+    _capi.check(rc, "satmi_cdcl_shrink_batch_device")

@@ -5,6 +5,7 @@ the lemmas the queries before it learned (satmi_cdcl_carry_batch_host).
     with Solver(bootstrap_with=formula) as s:
         s.solve(assumptions=[4, -7])      # True / False / None (conflict_limit reached)
         s.get_core()                      # after False: the assumptions to blame
+        s.solve(assumptions=[4, -7], minimal_core=True)     # ... and none of them a bystander
         s.add_clause([1, -3])
         s.solve()
 
@@ -15,7 +16,7 @@ lemmas would no longer follow and every later UNSAT answer would be unfounded.  
 that has to go later is added with a selector literal, [-s] + clause, and switched on by
 assuming s."""
 from . import _capi
-from .cdcl_sound import cdcl_carry_batch
+from .cdcl_sound import cdcl_carry_batch, cdcl_shrink_batch
 
 _SUMMED = ("conflicts", "decisions", "propagated", "rounds")
 
@@ -51,13 +52,18 @@ class Solver:
         for c in formula:
             self.add_clause(c)
 
-    def solve(self, assumptions=(), conflict_limit=0):
+    def solve(self, assumptions=(), conflict_limit=0, minimal_core=False):
         """Is the formula satisfiable with every assumption true?  True, False, or None when
         conflict_limit > 0 conflicts did not decide it; the next call goes on from the lemmas
         learned so far in all three cases.  Raises SatmiError when the search could not run
-        (the formula is beyond the kernel's layout, or the region's cap is reached)."""
+        (the formula is beyond the kernel's layout, or the region's cap is reached).
+        With `minimal_core` a False answer's core is shrunk in the same launch
+        (satmi_cdcl_shrink_batch_host): the formula is satisfiable with the core less any one
+        literal, unless a trial query reached conflict_limit and kept its literal unproven;
+        the lemmas of every trial are kept, and accum_stats counts the trials."""
         self._assumed = [int(a) for a in assumptions]
-        r = cdcl_carry_batch([self._clauses], [self._assumed], [self._lemmas], conflict_limit=conflict_limit,
+        query = cdcl_shrink_batch if minimal_core else cdcl_carry_batch
+        r = query([self._clauses], [self._assumed], [self._lemmas], conflict_limit=conflict_limit,
                              time_limit=self._time_limit)[0]
         self._last = None
         st = r["status"]
@@ -67,6 +73,8 @@ class Solver:
         for k in _SUMMED:
             self._stats[k] += r["counters"][k]
         self._stats["queries"] += 1
+        if minimal_core:
+            self._stats["trials"] = self._stats.get("trials", 0) + r["shrink"]["queries"] - 1
         self._last = r
         return r["sat"]
 
@@ -95,5 +103,6 @@ class Solver:
         return len(self._lemmas)
 
     def accum_stats(self):
-        """Conflicts, decisions, propagated literals and rounds, summed over the calls."""
+        """Conflicts, decisions, propagated literals and rounds, summed over the calls (and
+        "trials", the trial queries of the calls with minimal_core, once there was one)."""
         return dict(self._stats)

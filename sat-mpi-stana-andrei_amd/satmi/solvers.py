@@ -239,7 +239,7 @@ def resolution_witness(formula: Formula) -> Tuple[bool, Optional[Assignment]]:
     return _witnesses([formula], [r], stages_of_resolution, True, "resolution_witness")[0]
 
 
-def cdcl_sound_solve(formula: Formula, assumptions=None):
+def cdcl_sound_solve(formula: Formula, assumptions=None, minimal_core=False):
     """The library's own clause-learning decision procedure (csrc/cdcl_sound.hip):
     (True, model, None) with model {variable: bool} over the formula's variables, or
     (False, None, proof) where `proof` is the learned clauses in learning order, the empty
@@ -251,10 +251,15 @@ def cdcl_sound_solve(formula: Formula, assumptions=None):
     has a fourth member: (True, model, None, None), the model over the assumptions' variables
     too, or (False, None, proof, core), where `core` lists the assumptions to blame, the
     refuted one first ([]: the formula alone is unsatisfiable), and check_refutation holds for
-    the formula plus the core's literals as unit clauses."""
-    from .cdcl_sound import cdcl_assume_batch, cdcl_sound_batch
+    the formula plus the core's literals as unit clauses.
+    With `minimal_core` (and assumptions) the core is shrunk on the GPU until the formula is
+    satisfiable with the core less any one literal (cdcl_sound.cdcl_shrink_batch; a trial query
+    that the deadline cuts keeps its literal); `proof` then holds the lemmas of every query."""
+    from .cdcl_sound import cdcl_assume_batch, cdcl_shrink_batch, cdcl_sound_batch
     from .refute import proof_of_cdcl
-    if assumptions is not None:
+    if assumptions is not None and minimal_core:
+        r = cdcl_shrink_batch([list(formula)], [list(assumptions)], time_limit=_time_limit)[0]
+    elif assumptions is not None:
         r = cdcl_assume_batch([list(formula)], [list(assumptions)], time_limit=_time_limit)[0]
     else:
         r = cdcl_sound_batch([list(formula)], time_limit=_time_limit)[0]
