@@ -17,10 +17,11 @@ UNSAT, SAT, LIMIT, FULL, TOO_LARGE, ASSUMED = range(6)
 COUNTERS = R.COUNTERS
 
 
-def solve(formula, assumptions=(), conflict_limit=0):
+def solve(formula, assumptions=(), conflict_limit=0, *, halve=R.HALVE):
     """{"status", "counters": [8], "model": signed literals ascending by variable or None,
     "lemmas": the learned clauses in order, [] last when UNSAT or ASSUMED, "core": the failed
-    assumptions (ASSUMED), [] (UNSAT) or None}."""
+    assumptions (ASSUMED), [] (UNSAT) or None, "paths": cdcl_sound_rows.solve's}.  `halve` as
+    there."""
     clauses = [list(c) for c in formula]
     assume = list(assumptions)
     k = len(assume)
@@ -30,6 +31,7 @@ def solve(formula, assumptions=(), conflict_limit=0):
     phase = {v: False for v in occurs}
     n = dict.fromkeys(COUNTERS, 0)
     lemmas = []
+    paths = dict.fromkeys(R.PATHS, 0)
     core = None
     cur = 0
 
@@ -50,6 +52,7 @@ def solve(formula, assumptions=(), conflict_limit=0):
                     return i
                 if len(free) == 1:
                     (u,) = free
+                    paths["opposite offers lost"] += abs(u) in units and units[abs(u)][1] == -u
                     units.setdefault(abs(u), (i, u))
             if not units:
                 return None
@@ -66,8 +69,10 @@ def solve(formula, assumptions=(), conflict_limit=0):
                 if v != pvar and v not in seen and level[v] > 0:
                     seen.add(v)
                     count += level[v] == cur
+            top = idx
             while abs(trail[idx]) not in seen:
                 idx -= 1
+            paths["first-UIP walk gap"] = max(paths["first-UIP walk gap"], top - idx)
             p = trail[idx]
             pvar = abs(p)
             seen.discard(pvar)
@@ -76,7 +81,10 @@ def solve(formula, assumptions=(), conflict_limit=0):
             if count == 0:
                 break
             c = clauses[reason[pvar]]
-        return [-p] + [-l for l in reversed(trail[:idx + 1]) if abs(l) in seen]
+        low = [i for i in range(idx, -1, -1) if abs(trail[i]) in seen]
+        if low:
+            paths["collection walk gap"] = max(paths["collection walk gap"], idx - low[0])
+        return [-p] + [-trail[i] for i in low]
 
     def final(a):
         """The assumptions that made `a` false: `a`, then those reached from it through the
@@ -84,12 +92,15 @@ def solve(formula, assumptions=(), conflict_limit=0):
         out, seen = [a], set()
         if level[abs(a)] > 0:
             seen.add(abs(a))
+        gap = 0
         for l in reversed(trail):
             v = abs(l)
             if level[v] == 0:
                 break
             if v not in seen:
+                gap += 1
                 continue
+            paths["final walk gap"], gap = max(paths["final walk gap"], gap), 0
             if reason[v] is None:
                 out.append(l)
             else:
@@ -118,9 +129,10 @@ def solve(formula, assumptions=(), conflict_limit=0):
             while trail and level[abs(trail[-1])] > cur:
                 v = abs(trail.pop())
                 phase[v] = val.pop(v)
-            if n["conflicts"] % 256 == 0:
+            if halve[0] and n["conflicts"] % halve[0] == halve[1]:
+                paths["halvings"] += 1
                 for v in act:
-                    act[v] //= 2
+                    act[v] = (act[v] + halve[2]) // 2
             continue
         if cur < k:     # the next assumption's level
             a = assume[cur]
@@ -140,14 +152,16 @@ def solve(formula, assumptions=(), conflict_limit=0):
             status = SAT
             break
         v = max(cands, key=lambda x: (act[x], -x))
+        paths["decisions past lane 63 by activity"] += v > 64 and v != cands[0]
         cur += 1
         n["decisions"] += 1
         n["max_level"] = max(n["max_level"], cur)
         val[v], level[v], reason[v] = phase[v], cur, None
         trail.append(v if phase[v] else -v)
+    paths["deepest level"] = n["max_level"]
     return {"status": status, "counters": [n[c] for c in COUNTERS],
             "model": [v if val[v] else -v for v in occurs] if status == SAT else None, "lemmas": lemmas,
-            "core": core}
+            "core": core, "paths": paths}
 
 
 def rup(clauses, lemma):

@@ -30,24 +30,28 @@ def records(lemmas):
     return out
 
 
-def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=None):
+def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=None, *, halve=R.HALVE,
+          conflicts_before=0):
     """cdcl_assume_rows.solve's dict, where "lemmas" is the region's record list (the carried
     lemmas first, then those learned and written, [] last when UNSAT or ASSUMED), and with it
     "kept" (the non-empty records of the region: what the next query carries), "records" and
     "words" (info[0], info[1]: the closing record and a record that did not fit included),
     "flags" and "hits" (how often each of HITS occurred).  `room` = the region's words (None =
-    as many as needed), `nvars` = inst_nvars (None = the largest variable anywhere)."""
+    as many as needed), `nvars` = inst_nvars (None = the largest variable anywhere).  `halve` as in cdcl_sound_rows.solve;
+    a `conflicts_before` other than 0 is another rule: the halving keyed on a count that goes on
+    from the queries before."""
     clauses = [list(c) for c in formula]
     assume = list(assumptions)
     carried = [list(c) for c in carry]
     m, p, k = len(clauses), len(carried), len(assume)
     hits = dict.fromkeys(HITS, 0)
+    paths = dict.fromkeys(R.PATHS, 0)
     top = max([abs(l) for c in clauses + carried for l in c] + [abs(a) for a in assume] + [0])
     nv = top if nvars is None else nvars
 
     def ended(status, flags, kept):
         return {"status": status, "counters": [0] * len(COUNTERS), "model": None, "lemmas": [], "core": None,
-                "kept": kept, "records": 0, "words": 0, "flags": flags, "hits": hits}
+                "kept": kept, "records": 0, "words": 0, "flags": flags, "hits": hits, "paths": paths}
 
     def beyond(l):
         return l == 0 or l == I32_MIN or abs(l) > nv
@@ -90,6 +94,7 @@ def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=
                     return i
                 if len(free) == 1:
                     (u,) = free
+                    paths["opposite offers lost"] += abs(u) in units and units[abs(u)][1] == -u
                     units.setdefault(abs(u), (i, u))
             if not units:
                 return None
@@ -107,8 +112,10 @@ def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=
                 if v != pvar and v not in seen and level[v] > 0:
                     seen.add(v)
                     count += level[v] == cur
+            top = idx
             while abs(trail[idx]) not in seen:
                 idx -= 1
+            paths["first-UIP walk gap"] = max(paths["first-UIP walk gap"], top - idx)
             q = trail[idx]
             pvar = abs(q)
             seen.discard(pvar)
@@ -118,18 +125,24 @@ def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=
                 break
             c = clauses[reason[pvar]]
             hits[HITS[2]] += is_carried(reason[pvar])
-        return [-q] + [-l for l in reversed(trail[:idx + 1]) if abs(l) in seen]
+        low = [i for i in range(idx, -1, -1) if abs(trail[i]) in seen]
+        if low:
+            paths["collection walk gap"] = max(paths["collection walk gap"], idx - low[0])
+        return [-q] + [-trail[i] for i in low]
 
     def final(a):
         out, seen = [a], set()
         if level[abs(a)] > 0:
             seen.add(abs(a))
+        gap = 0
         for l in reversed(trail):
             v = abs(l)
             if level[v] == 0:
                 break
             if v not in seen:
+                gap += 1
                 continue
+            paths["final walk gap"], gap = max(paths["final walk gap"], gap), 0
             if reason[v] is None:
                 out.append(l)
             else:
@@ -171,9 +184,10 @@ def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=
             while trail and level[abs(trail[-1])] > cur:
                 v = abs(trail.pop())
                 phase[v] = val.pop(v)
-            if n["conflicts"] % 256 == 0:
+            if halve[0] and (conflicts_before + n["conflicts"]) % halve[0] == halve[1]:
+                paths["halvings"] += 1
                 for v in act:
-                    act[v] //= 2
+                    act[v] = (act[v] + halve[2]) // 2
             continue
         if cur < k:     # the next assumption's level
             a = assume[cur]
@@ -198,15 +212,17 @@ def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=
             status = SAT
             break
         v = max(cands, key=lambda x: (act[x], -x))
+        paths["decisions past lane 63 by activity"] += v > 64 and v != cands[0]
         cur += 1
         n["decisions"] += 1
         n["max_level"] = max(n["max_level"], cur)
         val[v], level[v], reason[v] = phase[v], cur, None
         trail.append(v if phase[v] else -v)
+    paths["deepest level"] = n["max_level"]
     return {"status": status, "counters": [n[c] for c in COUNTERS],
             "model": [v if val[v] else -v for v in occurs] if status == SAT else None, "lemmas": lemmas,
             "core": core, "kept": [c for c in lemmas if c], "records": nrec, "words": nwords,
-            "flags": TRUNCATED if status == FULL else 0, "hits": hits}
+            "flags": TRUNCATED if status == FULL else 0, "hits": hits, "paths": paths}
 
 
 def chain(queries, conflict_limit=0):

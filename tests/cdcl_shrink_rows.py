@@ -21,18 +21,20 @@ SHRINK = ("queries", "sat_trials", "assumed_trials", "limit_trials", "first_core
 TRUNCATED = C.TRUNCATED
 
 
-def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=None):
+def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=None, **rule):
     """cdcl_carry_rows.solve's dict for the whole chain ("hits" left out): the counters summed
     over the queries (max_level their maximum), "lemmas" the region's records at the end,
     "core" the final W, and with it "shrink" (the six words of SHRINK), "first" (query 0's
-    result) and "trials" (the (dropped literal, status) pairs in order)."""
+    result), "trials" (the (dropped literal, status) pairs in order) and "queries" (every
+    query's own result, query 0's first).  `rule` = cdcl_carry_rows.solve's keywords for
+    another rule, in every query."""
     clauses = [list(c) for c in formula]
     top = max([abs(l) for c in clauses + [list(c) for c in carry] for l in c] + [abs(a) for a in assumptions] + [0])
     nv = top if nvars is None else nvars
-    first = C.solve(clauses, assumptions, conflict_limit, carry, room, nv)
+    first = C.solve(clauses, assumptions, conflict_limit, carry, room, nv, **rule)
     out = {k: first[k] for k in ("status", "model", "lemmas", "core", "kept", "records", "words", "flags")}
     out["counters"] = list(first["counters"])
-    out["first"], out["trials"] = first, []
+    out["first"], out["trials"], out["queries"] = first, [], [first]
     n = dict.fromkeys(SHRINK, 0)
     n["queries"] = 1
     out["shrink"] = [n[k] for k in SHRINK]
@@ -42,7 +44,8 @@ def solve(formula, assumptions=(), conflict_limit=0, carry=(), room=None, nvars=
     n["first_core"] = len(W)
     while p < len(W):
         trial = W[:p] + W[p + 1:]
-        last = C.solve(clauses, trial, conflict_limit, last["kept"], room, nv)
+        last = C.solve(clauses, trial, conflict_limit, last["kept"], room, nv, **rule)
+        out["queries"].append(last)
         n["queries"] += 1
         out["trials"].append((W[p], last["status"]))
         for i, x in enumerate(last["counters"]):

@@ -6,7 +6,10 @@ The rule is include/satmi.h's (satmi_cdcl_sound_batch_device): rounds of unit
 propagation over formula and learned clauses under the assignment of the round's
 start, the lowest-indexed falsified clause as the conflict, the lowest-indexed
 unit clause as a variable's reason, first-UIP learning with level-0 literals
-dropped, integer activities halved every 256 conflicts, saved phases, no restarts."""
+dropped, integer activities halved every 256 conflicts, saved phases, no restarts.
+
+solve also reports which structural paths of the kernel the search went down (PATHS), and
+takes another halving than the rule's by keyword: both for tests/cdcl_sound_paths.py."""
 import random
 
 import refute_rows as rr
@@ -17,9 +20,18 @@ MAX_VARS = 8191      # SATMI_CDCL_SOUND_MAX_VARS
 SHORT_MAX = 8        # csrc/cdcl_sound.hip's CS_SHORT_MAX: the longest clause of the lane-per-clause form
 
 
-def solve(formula, conflict_limit=0):
+PATHS = ("halvings", "decisions past lane 63 by activity", "first-UIP walk gap", "collection walk gap",
+         "final walk gap", "deepest level", "opposite offers lost")
+HALVE = (256, 0, 0)     # the rule's halving: when conflicts % 256 == 0, rounding down
+# what is not the rule (tests/test_cdcl_sound_paths.py: every halving row tells each from it)
+NOT_THE_RULE = {"no halving": (0, 0, 0), "one conflict early": (256, 255, 0), "rounding up": (256, 0, 1)}
+
+
+def solve(formula, conflict_limit=0, *, halve=HALVE):
     """{"status", "counters": [8], "model": signed literals ascending by variable or None,
-    "lemmas": the learned clauses in order, [] last when UNSAT}."""
+    "lemmas": the learned clauses in order, [] last when UNSAT, "paths": how often, or how
+    far, the search went down each of PATHS (tests/cdcl_sound_paths.py)}.  `halve` = (period,
+    remainder, 1 to round up): another than HALVE is another rule."""
     clauses = [list(c) for c in formula]
     occurs = sorted({abs(l) for c in formula for l in c})
     val, level, reason, trail = {}, {}, {}, []
@@ -27,6 +39,7 @@ def solve(formula, conflict_limit=0):
     phase = {v: False for v in occurs}
     n = dict.fromkeys(COUNTERS, 0)
     lemmas = []
+    paths = dict.fromkeys(PATHS, 0)
     cur = 0
 
     def value(l):
@@ -46,6 +59,7 @@ def solve(formula, conflict_limit=0):
                     return i          # the lowest-indexed falsified clause; the round implies nothing
                 if len(free) == 1:
                     (u,) = free
+                    paths["opposite offers lost"] += abs(u) in units and units[abs(u)][1] == -u
                     units.setdefault(abs(u), (i, u))   # the lowest-indexed clause that implies the variable
             if not units:
                 return None
@@ -62,8 +76,10 @@ def solve(formula, conflict_limit=0):
                 if v != pvar and v not in seen and level[v] > 0:
                     seen.add(v)
                     count += level[v] == cur
+            top = idx
             while abs(trail[idx]) not in seen:
                 idx -= 1
+            paths["first-UIP walk gap"] = max(paths["first-UIP walk gap"], top - idx)
             p = trail[idx]
             pvar = abs(p)
             seen.discard(pvar)
@@ -72,7 +88,10 @@ def solve(formula, conflict_limit=0):
             if count == 0:
                 break
             c = clauses[reason[pvar]]
-        return [-p] + [-l for l in reversed(trail[:idx + 1]) if abs(l) in seen]
+        low = [i for i in range(idx, -1, -1) if abs(trail[i]) in seen]
+        if low:
+            paths["collection walk gap"] = max(paths["collection walk gap"], idx - low[0])
+        return [-p] + [-trail[i] for i in low]
 
     while True:
         confl = propagate()
@@ -96,22 +115,26 @@ def solve(formula, conflict_limit=0):
             while trail and level[abs(trail[-1])] > cur:
                 v = abs(trail.pop())
                 phase[v] = val.pop(v)
-            if n["conflicts"] % 256 == 0:
+            if halve[0] and n["conflicts"] % halve[0] == halve[1]:
+                paths["halvings"] += 1
                 for v in act:
-                    act[v] //= 2
+                    act[v] = (act[v] + halve[2]) // 2
             continue
         cands = [v for v in occurs if v not in val]
         if not cands:
             status = SAT
             break
         v = max(cands, key=lambda x: (act[x], -x))
+        paths["decisions past lane 63 by activity"] += v > 64 and v != cands[0]
         cur += 1
         n["decisions"] += 1
         n["max_level"] = max(n["max_level"], cur)
         val[v], level[v], reason[v] = phase[v], cur, None
         trail.append(v if phase[v] else -v)
+    paths["deepest level"] = n["max_level"]
     return {"status": status, "counters": [n[k] for k in COUNTERS],
-            "model": [v if val[v] else -v for v in occurs] if status == SAT else None, "lemmas": lemmas}
+            "model": [v if val[v] else -v for v in occurs] if status == SAT else None, "lemmas": lemmas,
+            "paths": paths}
 
 
 def region_words(lemmas):

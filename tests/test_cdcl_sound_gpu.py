@@ -101,7 +101,9 @@ def test_every_answer_is_certified_by_the_librarys_checkers():
 
 @pytest.mark.parametrize("holes", [5, 6])
 def test_pigeonhole_proofs_are_proven(holes):
-    """Held to soundness only: the proof is PROVEN, forwards and by the trim."""
+    """The proof is PROVEN, forwards and by the trim.  (Soundness alone here; PHP(6) word for word
+    against the rule, past its 256th conflict, is the row `php 6` of
+    tests/test_cdcl_sound_paths_gpu.py.)"""
     f = R.php(holes)
     r = cdcl_sound.cdcl_sound_batch([f])[0]
     assert r["sat"] is False and r["counters"]["learned"] > holes
